@@ -25,6 +25,15 @@ the timed region the step is repeated for >= --sustain seconds (`sustained`).
 `aux_rooflines` carries HBM roofline lines for the FFT form of the correlation
 and the volumetric / large in-plane mesh steps.  `cpu_baseline` times the CPU oracle (a NumPy/SciPy port
 of the reference algorithm) on a bounded sample of the same workload.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the line; `roofline` then holds the figures of the timed
+region's own launches.  Everything else above -- the un-pruned and other-pair
+roofline legs, `sustained`, `aux_rooflines`, `configs_legs`, `cpu_baseline`
+and, at N > 1, the communicating `multi_gpu` legs -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (the flow field
+and the relaxed mesh with its kinetic-energy history and step count) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -87,6 +96,31 @@ def mesh_inputs(flow, pad):
   return f[:, None].astype(np.float32)
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, flow, mesh_out):
+  """Writes what the last timed step returned to its caller as out_dir/<name>.npy:
+  the flow field (flow_field()), the relaxed mesh positions, the kinetic-energy
+  history and the number of steps run (relax_mesh()).  An array beyond its share
+  of DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its elements."""
+  x, e_kin, n_steps = mesh_out
+  arrays = {
+      'flow': np.asarray(flow, dtype=np.float32),
+      'mesh_x': np.asarray(x, dtype=np.float32),
+      'mesh_e_kin': np.asarray(e_kin, dtype=np.float64),
+      'mesh_steps': np.asarray([n_steps], dtype=np.float64),
+  }
+  share = DUMP_LIMIT_BYTES // len(arrays)
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in arrays.items():
+    if a.nbytes > share:
+      idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize,
+                                                    replace=False))
+      a = a.reshape(-1)[idx]
+    np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def build_sha():
   """Hash of the kernel sources in this tree (sofima_amd._build.source_hash)."""
   try:
@@ -139,6 +173,13 @@ def main():
                   help='extra leg: one [2,64,204,204] mesh split into BANDS bands '
                        'per rank, stepped by the C-side banded loop (RCCL halo '
                        'exchange between ranks)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run everything beyond the headline figure: the un-pruned '
+                       'and other-pair roofline legs, the sustained loop, aux_rooflines, '
+                       'configs_legs, the CPU baseline and, at N > 1, the communicating '
+                       'legs (each still subject to its --no-* / --sustain switch)')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='write what the last timed step computed as DIR/<name>.npy')
   args = ap.parse_args()
 
   if args.cpu_baseline_only:
@@ -262,7 +303,8 @@ def main():
     flow = flow_step()
     torch.cuda.synchronize(dev)
     b = time.perf_counter()
-    _, _, t_iters = mesh_step(prev_t)
+    mesh_out = mesh_step(prev_t)
+    t_iters = mesh_out[2]
     torch.cuda.synchronize(dev)
     c = time.perf_counter()
     t_flow += b - a
@@ -274,6 +316,9 @@ def main():
   _abi.check(lib.sfm_profile_read(C.byref(prof)))
 
   lap('timed_region')
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, flow, mesh_out)
+    lap('dump_outputs')
   times = torch.tensor([elapsed, t_flow, t_mesh], dtype=torch.float64,
                        device=dev if backend == 'nccl' else 'cpu')
   if world > 1:
@@ -375,7 +420,7 @@ def main():
         'tflops_at_this_patch_rate': round(
             fft_flop * world * n_patches * args.steps / t_flow / 1e12, 3),
         'direct_over_fft_flop': round(flop_per_patch / fft_flop, 1)}
-    legs = uses_mfma and not args.no_legs and world == 1
+    legs = args.full and uses_mfma and not args.no_legs and world == 1
     if legs:
       n_leg = max(args.steps, 3)
       pf_full, wall_full = timed_flow_leg(pre_t, post_t, False, n_leg)
@@ -406,8 +451,8 @@ def main():
                 'issued_frac'):
         if k in timed:
           roof[k] = timed[k]
-      roof['frac_is'] = ('pruned launch of the timed region (algorithmic; run without '
-                         '--no-legs at --gpus 1 for the un-pruned hardware leg)')
+      roof['frac_is'] = ('pruned launch of the timed region (algorithmic; run with --full '
+                         'and without --no-legs at --gpus 1 for the un-pruned hardware leg)')
 
   ms_ms, ms_n = prof.kernel_ms[1], prof.launches[1]
   mesh_obj = {
@@ -476,7 +521,7 @@ def main():
   # the same step is repeated back to back for >= --sustain seconds (all ranks).
   lap('roofline_legs')
   sustained = None
-  if args.sustain > 0:
+  if args.full and args.sustain > 0:
     barrier()
     s0 = time.perf_counter()
     n_sus = 0
@@ -502,12 +547,12 @@ def main():
 
   lap('sustain')
   aux = None
-  if world == 1 and not args.no_legs:
+  if args.full and world == 1 and not args.no_legs:
     aux = aux_legs(dev, args.seed)
     lap('aux_legs')
 
   cfg_legs = None
-  if world == 1 and not args.no_legs:
+  if args.full and world == 1 and not args.no_legs:
     cfg_legs = config_legs(dev, pre, args.seed)
     lap('config_legs')
 
@@ -551,16 +596,17 @@ def main():
   if cfg_legs:
     out['configs_legs'] = cfg_legs
 
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
     out['cpu_baseline'] = cpu_baseline(size, args.seed + rank, args.pair)
     lap('cpu_baseline')
 
-  # N > 1: the legs that really communicate (the timed default workload above
-  # is N independent tile pairs, no data-path collective).  They run LAST and
+  # N > 1 with --full (or --force-multi-gpu-legs): the legs that really
+  # communicate (the timed default workload above is N independent tile pairs,
+  # no data-path collective).  They run LAST and
   # under a watchdog: the headline numbers above are complete, and a leg that
   # fails or hangs (they are the least-exercised code: single-GPU boxes cannot
   # run them over RCCL) costs its own entry, never the line.
-  if (world > 1 or forced) and not args.no_multi_gpu_legs:
+  if ((world > 1 and args.full) or forced) and not args.no_multi_gpu_legs:
     import threading
     multi = {
         'backend': 'rccl' if backend == 'nccl' else backend,
@@ -1159,6 +1205,22 @@ def cpu_baseline(size, seed, pair='warped'):
   return json.loads(out.stdout.strip().splitlines()[-1])
 
 
+def usable_cpus():
+  """CPUs this process may really use: os.cpu_count() counts the whole host,
+  while the affinity mask or the OMP_NUM_THREADS the job was given can allow
+  far fewer (a pool sized past them only slows itself down)."""
+  n = os.cpu_count() or 1
+  try:
+    n = min(n, len(os.sched_getaffinity(0)))
+  except (AttributeError, OSError):
+    pass
+  try:
+    n = min(n, max(1, int(os.environ.get('OMP_NUM_THREADS', n))))
+  except ValueError:
+    pass
+  return n
+
+
 _CPU = {}
 
 
@@ -1185,12 +1247,12 @@ def _cpu_mesh_replica(seed):
 
 
 def cpu_baseline_child(size, seed, pair='warped'):
-  """The CPU oracle (a NumPy / SciPy port of the reference algorithm) on ALL host
-  cores: one process per core (fork), each correlating whole reference batches
+  """The CPU oracle (a NumPy / SciPy port of the reference algorithm) on ALL the
+  host cores it may use (usable_cpus): one process per core (fork), each correlating whole reference batches
   of the same pair (FFT form + peak statistics, single-threaded FFTs), then one
   independent 205^2 mesh relaxation per core."""
   import multiprocessing as mp
-  cores = os.cpu_count() or 1
+  cores = usable_cpus()
   pre, post = synth_pair(size, seed, warp=WARP if pair == 'warped' else None)
   n_grid = (size - (PATCH - STEP)) // STEP
   # reference batches small enough that every host core gets at least one

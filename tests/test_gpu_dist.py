@@ -284,7 +284,7 @@ def test_bench_runs_as_two_ranks(gpu):
   env = dict(os.environ, SFM_BENCH_BACKEND='gloo', SFM_BENCH_ONE_DEVICE='1')
   cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--size', '1024',
          '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--mesh-iters', '100',
-         '--sustain', '0.5']
+         '--sustain', '0.5', '--full']
   out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
   assert out.returncode == 0, out.stderr[-2000:]
   lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -297,7 +297,7 @@ def test_bench_runs_as_two_ranks(gpu):
   assert abs(line['value'] - want) <= 1e-6 * want
   assert line['roofline'] and line['mesh']['value'] > 0
   assert line['sustained']['steps'] >= 1
-  # the communicating legs are part of the default N > 1 line
+  # the communicating legs are part of the --full N > 1 line
   mg = line['multi_gpu']
   assert mg['ranks_seen'] == 2 and mg['backend'] == 'gloo'
   chain = mg['section_chain']
@@ -347,6 +347,45 @@ def test_bench_multi_gpu_legs_over_rccl_at_world_size_one(gpu):
   band = mg['mesh_sharded']
   assert band['bands_per_rank'] == 2 and 'RCCL' in band['transport']
   assert band['banded_us_per_step'] > 0
+
+
+def test_bench_plain_run_dumps_its_last_step(gpu, tmp_path):
+  """A plain `bench.py --gpus 1` line times exactly --steps steps and carries
+  none of the --full legs; --dump-outputs writes what the last timed step
+  returned, and the flow field equals a direct flow_field() call on the
+  bench's own seeded pair."""
+  import json
+  import os
+  import subprocess
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--size', '1024',
+         '--steps', '2', '--warmup', '1', '--mesh-iters', '100',
+         '--dump-outputs', str(tmp_path)]
+  out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+  assert out.returncode == 0, out.stderr[-2000:]
+  lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+  assert len(lines) == 1, out.stdout[-2000:]
+  line = json.loads(lines[0])
+  assert line['steps'] == 2 and line['warmup'] == 1 and line['ms_per_step'] > 0
+  assert line['unit'] == 'Mpix/s' and line['higher_is_better'] is True
+  for key in ('sustained', 'aux_rooflines', 'configs_legs', 'cpu_baseline', 'multi_gpu'):
+    assert key not in line, key
+  assert 'unpruned' not in (line['roofline'] or {})
+
+  import bench
+  from sofima_amd import flow_field
+  flow = np.load(tmp_path / 'flow.npy')
+  x = np.load(tmp_path / 'mesh_x.npy')
+  steps = np.load(tmp_path / 'mesh_steps.npy')
+  assert flow.dtype == np.float32 and flow.shape == (4, 22, 22)
+  assert x.dtype == np.float32 and x.shape == (2, 1, 26, 26)
+  assert steps.tolist() == [100.0]
+  assert np.load(tmp_path / 'mesh_e_kin.npy').dtype == np.float64
+  pre, post = bench.synth_pair(1024, 1002, warp=bench.WARP)
+  want = flow_field.JAXMaskedXCorrWithStatsCalculator().flow_field(
+      pre, post, bench.PATCH, bench.STEP, batch_size=bench.BATCH)
+  np.testing.assert_array_equal(flow, want)
 
 
 def _two_rank_band_worker(rank, world_size, port, out_dir):

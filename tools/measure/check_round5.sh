@@ -6,7 +6,7 @@ cd $R
 SHA=$(python -c "from sofima_amd import _build; print(_build.source_hash())")
 echo $SHA > $O/build_sha.txt
 timeout 2700 python -m pytest tests -m gpu -q -rf --tb=line -x 2>&1 | grep -E "^FAILED|passed|failed|error|Error" | tail -12 > $O/pytest.log
-timeout 900 python bench.py --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --no-cpu-baseline --no-legs --sustain 0"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o r5 -- $B --steps 3 --warmup 1 > $O/trace.log 2>&1

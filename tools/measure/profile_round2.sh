@@ -5,14 +5,14 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r2; mkdir -p $O
 cd $R
 SHA=$(cat $R/.build_sha 2>/dev/null || echo unknown)
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|error" | tail -4 > $O/pytest.log
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o r2 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o r2 -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
 python $R/tools/rocpd_summary.py $(find $O/trace -name '*.db' | head -1) > $O/trace_summary.md 2>&1
-timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o f -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --mesh-iters 1000 > $O/pmc_f.log 2>&1
-timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o w -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --mesh-iters 1000 > $O/pmc_w.log 2>&1
+timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o f -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --mesh-iters 1000 > $O/pmc_f.log 2>&1
+timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o w -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --mesh-iters 1000 > $O/pmc_w.log 2>&1
 python $R/tools/pmc_summary.py $(find $O/pmc_f -name '*counter_collection.csv' | head -1) $(find $O/pmc_w -name '*counter_collection.csv' | head -1) $O/pmc_traffic.json $SHA 40401 > $O/pmc_summary.log 2>&1
-timeout 600 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq -o sq -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --mesh-iters 10 > $O/pmc_sq.log 2>&1
+timeout 600 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq -o sq -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --mesh-iters 10 > $O/pmc_sq.log 2>&1
 python - <<PY > $O/pmc_sq_summary.txt 2>&1
 import csv, collections, glob
 f = glob.glob('$O/pmc_sq/**/*counter_collection.csv', recursive=True)[0]
@@ -32,6 +32,6 @@ python $R/tools/measure/pipeline_time.py > $O/pipeline_time.log 2>&1
 python $R/tools/measure/offset_time.py > $O/offset_time.log 2>&1
 python $R/tools/measure/power_probe.py > $O/power_probe.log 2>&1
 python $R/tools/measure/prune_time.py > $O/prune_time.log 2>&1
-SFM_MFMA_PRUNE=0 timeout 600 python $R/bench.py --no-cpu-baseline > $O/bench_noprune.json 2> /dev/null
+SFM_MFMA_PRUNE=0 timeout 600 python $R/bench.py --full --no-cpu-baseline > $O/bench_noprune.json 2> /dev/null
 rm -rf $O/trace/*/*.db.tmp; find $O -name '*.db' -size +20M -delete
 cat $O/pytest.log $O/bench.json; tail -3 $O/bench.err

@@ -6,14 +6,14 @@ cd $R
 SHA=$(python -c "from sofima_amd import _build; print(_build.source_hash())")
 echo $SHA > $O/build_sha.txt
 timeout 2400 python -m pytest tests -m gpu -q -rf --tb=line 2>&1 | grep -E "^FAILED|passed|failed|error" | tail -12 > $O/pytest.log
-timeout 900 python bench.py --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 # production launches only in the traced / counted runs: no un-pruned legs, no sustained loop
 B="python $R/bench.py --no-cpu-baseline --no-legs --sustain 0"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o r4 -- $B --steps 3 --warmup 1 > $O/trace.log 2>&1
 python $R/tools/rocpd_summary.py $(find $O/trace -name '*.db' | head -1) > $O/trace_summary.md 2>&1
 # the same with the roofline legs on (un-pruned pair, other pair, aux_rooflines, configs legs)
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace_aux -o r4 -- python $R/bench.py --no-cpu-baseline --sustain 0 --steps 1 --warmup 1 > $O/trace_aux.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace_aux -o r4 -- python $R/bench.py --full --no-cpu-baseline --sustain 0 --steps 1 --warmup 1 > $O/trace_aux.log 2>&1
 python $R/tools/rocpd_summary.py $(find $O/trace_aux -name '*.db' | head -1) > $O/trace_aux_summary.md 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o f -- $B --steps 1 --warmup 1 > $O/pmc_f.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o w -- $B --steps 1 --warmup 1 > $O/pmc_w.log 2>&1

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 B="python $R/bench.py --no-cpu-baseline --no-legs --sustain 0"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace -o r5 -- $B --steps 3 --warmup 1 > $O/trace.log 2>&1
 python $R/tools/rocpd_summary.py $(find $O/trace -name '*.db' | head -1) > $O/trace_summary.md 2>&1
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace_aux -o r5 -- python $R/bench.py --no-cpu-baseline --sustain 0 --steps 1 --warmup 1 > $O/trace_aux.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace_aux -o r5 -- python $R/bench.py --full --no-cpu-baseline --sustain 0 --steps 1 --warmup 1 > $O/trace_aux.log 2>&1
 python $R/tools/rocpd_summary.py $(find $O/trace_aux -name '*.db' | head -1) > $O/trace_aux_summary.md 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_f -o f -- $B --steps 1 --warmup 1 > $O/pmc_f.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_w -o w -- $B --steps 1 --warmup 1 > $O/pmc_w.log 2>&1
@@ -43,7 +43,7 @@ cp $R/gpurun_out/pmc_aux/traffic_aux.json $O/pmc_traffic_aux.json
 cp $O/pmc_traffic.json $R/profiles/r05_pmc_traffic.json
 cp $O/pmc_traffic_aux.json $R/profiles/r05_pmc_traffic_aux.json
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err
 python $R/tools/measure/mesh_time.py 2>&1 | grep -v amdgpu > $O/mesh_time.log
 python $R/tools/measure/montage_time.py > $O/montage_time.log 2>&1
 python $R/tools/measure/masked_time.py 2>&1 | grep -v amdgpu > $O/masked_time.log

@@ -48,7 +48,7 @@ def main():
          f'--nproc-per-node={args.ranks}', '--master-addr', '127.0.0.1',
          '--master-port', str(port), os.path.join(ROOT, 'bench.py'),
          '--gpus', str(args.ranks), '--steps', str(args.steps), '--warmup', str(args.warmup),
-         '--size', str(args.size)]
+         '--size', str(args.size), '--full']
   t0 = time.time()
   try:
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT,
