@@ -76,18 +76,9 @@ int sfm_device_count(int* count);
  *   SFM_MFMA_NARROW=n     lazy path: widest in-flight narrowing of a row loop (outer column
  *                         tiles dropped once proved cold; default: down to the four
  *                         central tiles; 0: never)
- *   SFM_MFMA_WIDEN=1      lazy path: the store requests a patch starts with are widened
- *                         by one row tile (fewer recomputed tiles, more finished ones)
  *   SFM_MFMA_LAZYG=0      the prep kernel writes the whole correction table (default, pruned
  *                         flow launches: the finishing tiles build their 16 rows; the prep pass
  *                         then keeps no patch in LDS)
- *   SFM_MFMA_XCD=1        one patch queue per XCD (measured: no gain) instead of a flat one
- *   SFM_MFMA_PIPE=1       160-wide flow launches as a cross-patch pipeline: one workgroup of
- *                         eight waves per CU, two patch slots in LDS, the tile queue running
- *                         across the patch boundary (built in round 6, measured 3-4 % SLOWER
- *                         than two four-wave workgroups: profiles/r06_xcorr_phase_ticks.txt)
- *   SFM_MFMA_PIPE_ADMIT=n pipeline: tiles of a patch handed out before its first tile is done
- *                         (default 2)
  *   (measurement-only, honoured by a library built with -DSFM_MEASUREMENT_SWITCHES only --
  *   sfm_get_option("SFM_BUILD_MEASUREMENT_SWITCHES") = "1"; the production build ignores them:)
  *   SFM_MFMA_PROBE=0      no seed probe in front of the pruning
@@ -107,9 +98,6 @@ int sfm_device_count(int* count);
  *   SFM_MESH_PERSISTENT=0 / SFM_MESH_SPECULATE=0 / SFM_MESH_TILED=0 /
  *   SFM_MESH_SMALL=0 / SFM_MESH_FUSE_TARGET=0
  *                         fall back to the simpler integrator
- *   SFM_MESH_PERSIST3D=1  volumetric montage (native target mesh): every step of a chunk in ONE
- *                         launch with grid barriers (built in round 6: bit-identical, 2 x SLOWER
- *                         than the four launches per step it replaces, which stay the default)
  *   SFM_MESH_MARCH3D=0|1  default-link volumes (elastic_mesh_3d): the z-march integrator that
  *                         evaluates every spring once -- never / for every volume (default:
  *                         from 1.5 * 10^6 nodes on).  Forces bit-identical to the per-node kernel.

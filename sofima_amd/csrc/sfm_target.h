@@ -1,8 +1,7 @@
-// Device code shared by the target-mesh kernel (sfm_maps.hip) and the fused
-// volumetric montage step (sfm_mesh.hip): JAX's order-1 map_coordinates, the
-// per-tile neighbour entries of stitch_elastic.compute_target_mesh
-// (stitch_elastic.py:456-676) and the target of ONE node.  Both translation
-// units are compiled with -ffp-contract=off: the same float operations.
+// Device code of the target-mesh kernel (sfm_maps.hip): JAX's order-1
+// map_coordinates, the per-tile neighbour entries of
+// stitch_elastic.compute_target_mesh (stitch_elastic.py:456-676) and the target
+// of ONE node.  Compiled with -ffp-contract=off.
 #ifndef SFM_TARGET_H_
 #define SFM_TARGET_H_
 

@@ -232,13 +232,6 @@ struct MfmaArgs {
   long long s_stride; // padded surface: floats per patch = 16 * NP * sx_pitch
   // dynamic patch queue (NULL: static striding over the workgroups)
   int* work_counter;
-  // XCD-sharded form of the queue: the patches are cut into 8 contiguous ranges
-  // (partition k = the blocks b == k mod 8 of the prep kernel, which the
-  // dispatcher places on XCD k), every XCD has its own head word (128 bytes
-  // apart) and a workgroup draws from the range of the XCD it runs on, then
-  // steals from the others.  Neighbouring patches overlap by 75 %: their pixels
-  // are then fetched once per XCD L2 instead of once per L2.
-  int* xcd_heads;
   // shader-clock probe: workgroup 0 leaves (core cycles, 10 ns wall ticks) of its
   // residency here (bench.py reports the sustained clock under this kernel);
   // clk[2]: dy tiles skipped by the pruning (low word) / drawn (high word), whole
@@ -253,7 +246,6 @@ struct MfmaArgs {
   int prune;
   int touch_all;      // lazy modes: pull the whole correction table into L2, not only the requested tiles' rows (SFM_MFMA_TOUCH_ALL=1)
   int narrow;         // lazy modes: row loops drop provably cold outer column tiles in flight (SFM_MFMA_NARROW=0: off)
-  int widen;          // initial store requests: the previous need mask, widened by a tile (SFM_MFMA_WIDEN=1)
   int early;          // lazy modes: abandon provably cold tiles inside the row loop (least distance of two tests, row groups; 0 = off)
   int count_tiles;    // report the pruning counts through clk (timing hooks on)
   int probe;          // seed the running maximum from a probe block (see the kernel)
@@ -269,8 +261,6 @@ struct MfmaArgs {
   int* c16;           // [B, c16_stride]: [2][Py / 16 + 1][Px] column sums, then T[Py + 1]
   long long c16_stride;
   int nq;             // column tiles of the kernel variant
-  int slot_bytes;     // kModePipe: LDS bytes of one patch slot (multiple of 16)
-  int pipe_admit;     // kModePipe: tiles of a patch that may be drawn before its first tile is done
   int prune_k[4];     // outer column tiles (each side) of the row-loop variants (ascending)
 };
 
@@ -278,26 +268,6 @@ __device__ __forceinline__ unsigned load_u32_guarded(const unsigned* base,
                                                      long long idx,
                                                      long long n_words) {
   return (idx >= 0 && idx < n_words) ? base[idx] : 0u;
-}
-
-constexpr int kXcds = 8;
-constexpr int kHeadPitch = 32;   // ints between the per-XCD queue heads
-
-// Range of XCD partition k of n items: as many items as there are indices
-// b == k (mod 8) below n, partitions laid out one after the other.
-__host__ __device__ __forceinline__ int xcd_part_len(int n, int k) { return (n - k + kXcds - 1) / kXcds; }
-__host__ __device__ __forceinline__ int xcd_part_base(int n, int k) {
-  int base = 0;
-  for (int i = 0; i < k; ++i) base += xcd_part_len(n, i);
-  return base;
-}
-
-// Patch of prep block `blk`: block b is dispatched to XCD b mod 8 (observed
-// placement; only speed depends on it), so it prepares an item of partition b mod 8.
-__device__ __forceinline__ int xcd_block_item(const MfmaArgs& a, int blk, int n) {
-  if (!a.xcd_heads) return blk;
-  const int k = blk % kXcds;
-  return xcd_part_base(n, k) + blk / kXcds;
 }
 
 // ---------------------------------------------------------------------------
@@ -308,11 +278,9 @@ __global__ void __launch_bounds__(kThreads) mfma_prep_kernel(MfmaArgs a) {
     *a.work_counter = 0;  // the correlation kernel's patch queue
   if (a.clk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     a.clk[2] = a.clk[3] = a.clk[4] = 0;
-  if (a.xcd_heads && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < kXcds)
-    a.xcd_heads[kHeadPitch * threadIdx.x] = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int red[3][kThreads];
-  const int b = xcd_block_item(a, blockIdx.x, a.batch), s = blockIdx.y;
+  const int b = blockIdx.x, s = blockIdx.y;
   const int py = s == 0 ? a.P[0] : a.Q[0];
   const int px = s == 0 ? a.P[1] : a.Q[1];
   const int H = a.ishape[s][0], W = a.ishape[s][1];
@@ -1428,12 +1396,9 @@ mfma_prep_same_kernel(MfmaArgs a) {
   if (a.work_counter && blockIdx.x == 0 && threadIdx.x == 0)
     *a.work_counter = 0;  // the correlation kernel's patch queue
   if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) a.clk[2] = a.clk[3] = a.clk[4] = 0;  // tile counts
-  if (a.xcd_heads && blockIdx.x == 0 && threadIdx.x < kXcds)
-    a.xcd_heads[kHeadPitch * threadIdx.x] = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ PrepTables<kPrepWavesAlone, kBoundRows, LAZY> tables;
-  prep_same_body<kPrepWavesAlone, kBoundRows, LAZY>(a, xcd_block_item(a, blockIdx.x, a.batch),
-                                                    smem, &tables);
+  prep_same_body<kPrepWavesAlone, kBoundRows, LAZY>(a, blockIdx.x, smem, &tables);
 }
 
 // ---------------------------------------------------------------------------
@@ -1454,15 +1419,13 @@ struct StagePlane {
 
 constexpr int kStageBatch = 7;
 
-// (first, limit: the range of work items this call stages -- everything by default)
 template <int NT = kThreads>
 __device__ __forceinline__ void stage_patches(const StagePlane& p0, const StagePlane& p1,
-                                              const int tid, const int first = 0,
-                                              const int limit = 0x7fffffff) {
+                                              const int tid) {
   const StagePlane* pl[2] = {&p0, &p1};
   const int n_items0 = p0.py * p0.n_chunks, n_items1 = p1.py * p1.n_chunks;
-  const int n_max = min(max(n_items0, n_items1), limit);
-  for (int item0 = first + tid; item0 < n_max; item0 += NT * kStageBatch) {
+  const int n_max = max(n_items0, n_items1);
+  for (int item0 = tid; item0 < n_max; item0 += NT * kStageBatch) {
     v4i w[2][kStageBatch];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -1578,7 +1541,7 @@ __device__ void stage_plane(const unsigned char* __restrict__ img, long long img
 // Masked path prep: clamped origins in image and mask, masked mean, centre.
 __global__ void __launch_bounds__(kThreads) mfma_prep_masked_kernel(MfmaArgs a) {
   __shared__ int red[4][kThreads];
-  const int b = xcd_block_item(a, blockIdx.x, a.batch), s = blockIdx.y;
+  const int b = blockIdx.x, s = blockIdx.y;
   const int py = s == 0 ? a.P[0] : a.Q[0];
   const int px = s == 0 ? a.P[1] : a.Q[1];
   const int H = a.ishape[s][0], W = a.ishape[s][1];
@@ -2557,11 +2520,6 @@ constexpr int kModeSameLazy = 4, kModeSameExactLazy = 5;
 // kModeSameExactLazy with the correction table built in the epilogue of the tiles
 // that are stored (MfmaArgs::lazy_g; Py a multiple of 16): no table G in memory.
 constexpr int kModeSameExactLazyG = 6;
-// kModeSameExactLazyG as a cross-patch pipeline: ONE workgroup of eight waves per CU, TWO
-// patch slots in LDS, the tile queue running across the patch boundary (see the kernel).
-constexpr int kModePipe = 7;
-constexpr int kPipeCtl = 32;  // ints of a slot's control header (behind its lazy-store state;
-                              // 256 ints of seed-probe sums follow)
 
 // Inclusive add scan over the 16 lanes of a DPP row (the 16 columns of a tile).
 __device__ __forceinline__ int row16_scan_incl(int v) {
@@ -2641,33 +2599,6 @@ __global__ void __launch_bounds__(kThreads) mfma_first_peak_kernel(MfmaArgs a) {
   wave_first_peak(a, b, a.surface + b * a.s_stride, a.S[0], a.S[1], &s_cand[wave]);
 }
 
-// XCD-sharded queue: next item of this workgroup (n_items: none left).  Called
-// by all threads; `state` (thread 0 only): bits 0..2 the partition drawn from,
-// bits 8..15 the partitions found empty.
-__device__ __forceinline__ int pull_item(const MfmaArgs& a, int n_items, int* state,
-                                         int* next_lds) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int item = n_items, st = *state;
-    for (int tries = 0; tries < kXcds; ++tries) {
-      const int x = st & 7;
-      if (!((st >> (8 + x)) & 1)) {
-        const int p = atomicAdd(&a.xcd_heads[kHeadPitch * x], 1);
-        if (p < xcd_part_len(n_items, x)) {
-          item = xcd_part_base(n_items, x) + p;
-          break;
-        }
-        st |= 1 << (8 + x);
-      }
-      st = (st & ~7) | ((x + 1) & 7);   // steal from the next XCD's range
-    }
-    *state = st;
-    *next_lds = item;
-  }
-  __syncthreads();
-  return __builtin_amdgcn_readfirstlane(*next_lds);
-}
-
 // Next patch of this workgroup; called by all threads at the end of a patch.
 __device__ __forceinline__ int next_patch(const MfmaArgs& a, int b, int* next_lds) {
   if (!a.work_counter) return b + gridDim.x;
@@ -2679,9 +2610,8 @@ __device__ __forceinline__ int next_patch(const MfmaArgs& a, int b, int* next_ld
 }
 
 template <int NCA, int NCE, int MODE>
-__global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
-                                  : (NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_WAVES : kThreads,
-                                  (MODE == kModePipe || NCA > 10) ? 1 : 2) xcorr_mfma_kernel(MfmaArgs a) {
+__global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_WAVES : kThreads,
+                                  NCA > 10 ? 1 : 2) xcorr_mfma_kernel(MfmaArgs a) {
   // Search-window geometry (NCA > 10: pre patches 161 .. 320 wide against a post patch of up
   // to 160, processor/flow.py:577,792-803).  The pre patch alone is up to 119 KB of LDS, so a
   // CU holds ONE workgroup = one wave per SIMD -- which then owns the SIMD's whole register
@@ -2690,25 +2620,9 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
   // lower one (the fragments of the next row group are in flight while the 165 .. 220 matrix
   // instructions of this one issue).  kModeGeneral semantics; no pruning.  (That is the FIRST
   // form, SFM_WIDE_HALVES=0; the default is the second one, WIDE8 below.)
-  // Cross-patch pipeline (kModePipe; everything else is kModeSameExactLazyG).  The other
-  // modes run two workgroups of four waves per CU, each on its own patch, and every patch
-  // has phases in which its four waves wait for each other: the staging round trip, the
-  // seed probe's barrier, the waves that find the tile queue empty while the long tiles of
-  // the patch drain, the publication barrier.  Here ONE workgroup of EIGHT waves owns the
-  // CU and LDS holds TWO patch slots (pixels, 1-D arrays, bounds, lazy-store state, a
-  // control header each: 2 x 72 KB at 160^2).  A wave is not bound to a slot: it draws a
-  // row tile from whichever slot has one (control word = generation << 8 | next tile, so
-  // the draw is atomic with the patch's identity), and there is no workgroup barrier after
-  // start-up.  The wave whose tile completes a patch (per-slot completion counter) is its
-  // CLOSER: alone it runs the end-of-patch pass (recomputation of band tiles that finished
-  // un-stored, against the final maximum), publishes the patch, claims the next patch from
-  // the global queue, stages it into the slot it just freed (pixels, tables, seed probe,
-  // table touches -- one wave's loads, while the other seven work on the other slot) and
-  // re-arms the slot's control word.  The state a slot carries from patch to patch (seed
-  // block, previous need mask, hot columns) stays with the slot, i.e. every slot behaves
-  // like a workgroup of the other modes; results do not depend on any of it.
-  constexpr bool PIPE = MODE == kModePipe;
-  constexpr bool LAZYG = MODE == kModeSameExactLazyG || PIPE;
+  // The other variants (NCA <= 10) run two workgroups of four waves per CU, each on its own
+  // patch; the waves of a workgroup draw the row tiles of that patch.
+  constexpr bool LAZYG = MODE == kModeSameExactLazyG;
   constexpr bool SAME = MODE == kModeSame || MODE == kModeSameExact || MODE == kModeSameLazy ||
                         MODE == kModeSameExactLazy || LAZYG;
   constexpr bool EXACT = MODE == kModeSameExact || MODE == kModeSameExactLazy || LAZYG;
@@ -2725,7 +2639,6 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float touch_junk[kThreads];  // sink of the LDS-direct G touches
   __shared__ int probe_lds[kThreads];     // K-split sums of the seed probe (a.prune)
-  // (kModePipe: everything below exists once per slot, `bind_slot` re-points the names)
   unsigned char* A_lds = smem;
   unsigned char* B_lds = smem + a.a_bytes;
   float* R_lds = reinterpret_cast<float*>(smem + a.a_bytes + a.b_bytes);
@@ -2753,32 +2666,6 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
   int* lz_ks = lz_cq + 4;
   // lz_rows[p]: first | last << 8 row (0 .. 15) of tile p with a possibly hot element
   int* lz_rows = lz_ks + 32;
-  // kModePipe, control header of a slot:
-  //   [0] generation << 8 | next tile of the tile order (>= n_order: nothing to draw; written
-  //       by the opener LAST, so a successful draw implies a completely staged patch)
-  //   [1] tiles of the patch that are done (pruned, abandoned, cold or finished)
-  //   [2] patch index   [3] slot retired (no patch left for it)
-  //   [4..7] float bits of mean_A - c_A, mean_B - c_B, const_a, const_b of the patch
-  int* ctl = lz_rows + 32;
-  int* pr_lds = probe_lds;   // seed-probe sums (kModePipe: the slot's own 256 words)
-  auto bind_slot = [&](int s) {
-    unsigned char* base = smem + s * a.slot_bytes;
-    A_lds = base;
-    B_lds = base + a.a_bytes;
-    R_lds = reinterpret_cast<float*>(base + a.a_bytes + a.b_bytes);
-    pmax_lds = reinterpret_cast<int*>(base + a.a_bytes + a.b_bytes + a.r_bytes);
-    hot_lds = pmax_lds + 1;
-    tb_lds = reinterpret_cast<float*>(pmax_lds + 4);
-    best_lds = reinterpret_cast<int*>(tb_lds + kBoundStride);
-    lz = best_lds + 8;
-    lz_tmax = reinterpret_cast<float*>(lz + 4);
-    lz_prev = reinterpret_cast<int*>(lz_tmax + 31);
-    lz_cq = lz_prev + 1;
-    lz_ks = lz_cq + 4;
-    lz_rows = lz_ks + 32;
-    ctl = lz_rows + 32;
-    pr_lds = ctl + kPipeCtl;
-  };
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 15, g = lane >> 4;
@@ -2787,26 +2674,11 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
 
   const long long probe_c0 = clock64(), probe_w0 = wall_clock64();
   // Zero the whole LDS image once: pad rows / margins stay zero afterwards.
-  for (int i = threadIdx.x * 16; i < (PIPE ? 2 * a.slot_bytes : a.a_bytes + a.b_bytes);
-       i += (PIPE ? 2 * kThreads : WIDE8 ? 64 * SFM_WIDE_WAVES : kThreads) * 16)
+  for (int i = threadIdx.x * 16; i < a.a_bytes + a.b_bytes;
+       i += (WIDE8 ? 64 * SFM_WIDE_WAVES : kThreads) * 16)
     *reinterpret_cast<v4i*>(smem + i) = v4i{0, 0, 0, 0};
-  if constexpr (PIPE) {
-    __syncthreads();
-    if (lane == 0 && wave < 2) {
-      bind_slot(wave);
-      *best_lds = (((a.Q[0] - 1) / 16) << 8) | ((a.Q[1] - 1) / 16);  // the zero shift
-      best_lds[2] = 1;
-      lz_cq[0] = NQ;
-      lz_cq[1] = -1;
-      lz_cq[2] = lz_cq[3] = (a.Q[1] - 1) / 16;
-      ctl[0] = 255;    // generation 0, nothing to draw
-      ctl[2] = -1;
-    }
-    bind_slot(0);
-    __syncthreads();
-  }
 
-  if (!PIPE && SAME && (a.prune || LAZY) && threadIdx.x == 0) {
+  if (SAME && (a.prune || LAZY) && threadIdx.x == 0) {
     *best_lds = (((a.Q[0] - 1) / 16) << 8) | ((a.Q[1] - 1) / 16);  // the zero shift
     best_lds[2] = 1;  // pruning events of the previous patch (optimistic start)
     best_lds[3] = 0;  // patches of this workgroup so far
@@ -2849,20 +2721,9 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
   // Work items: patches, or the extra (patch, operand-plane pair) passes of
   // the masked path (see masked_classify_kernel).
   const int n_items = (RAW && a.list) ? *a.n_list : a.batch;
-  // HW_REG_XCC_ID (20), bits [3:0]: the XCD this workgroup runs on
-  int q_state = a.xcd_heads ? static_cast<int>(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7) : 0;
-  // (g0, gs: first row group and stride of the calling wave; alone: no other wave takes part)
-  // (kind 0: the four waves of a workgroup, sums through LDS atomics, barrier, seed;
-  // kind 2, kModePipe: this wave's share of the row groups into the slot's sums only --
-  // seed_finish() follows when every share is in)
-  auto seed_finish = [&]() {
-    int sm = max(max(pr_lds[lane], pr_lds[64 + lane]), max(pr_lds[128 + lane], pr_lds[192 + lane]));
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sm = max(sm, __shfl_xor(sm, d, 64));
-    const float m_lo = __int2float_rd(sm) - tb_lds[kBoundCorr];
-    if (lane == 0 && m_lo > 0.f) atomicMax(pmax_lds, __float_as_int(m_lo));
-  };
-  auto seed_probe = [&](const int g0, const int gs, const int kind) {
+  // (g0, gs: first row group and stride of the calling wave; the four waves of a
+  // workgroup, sums through LDS atomics, barrier, seed)
+  auto seed_probe = [&](const int g0, const int gs) {
       // Seed of the running maximum.  The first tiles are drawn before any tile
       // has finished, i.e. with nothing to prune against.  So the 16 x 16 block of
       // shifts that held the previous patch's maximum is evaluated first, its
@@ -2923,198 +2784,16 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
 #pragma unroll
       for (int r = 0; r < 4; ++r) pacc[r] += pacc2[r];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) atomicAdd(&pr_lds[r * 64 + lane], pacc[r]);
-      if (kind == 2) return;
+      for (int r = 0; r < 4; ++r) atomicAdd(&probe_lds[r * 64 + lane], pacc[r]);
       __syncthreads();
-      seed_finish();
-  };
-  // kModePipe: opening a slot, i.e. everything the other modes do per patch with 256
-  // threads and three barriers (staging, tables, state reset, seed probe, table touches),
-  // cut into UNITS that any wave without a tile can take:
-  //   unit 0            (the closer itself) the 1-D arrays, the pruning bounds, the zeroed
-  //                     probe sums, the table touches
-  //   units 1 .. NA     staging: 7 x 64 sixteen-byte items of either patch each
-  //   units NA+1 .. +NB the seed probe: every NB-th row group of the probe block (only
-  //                     after units 0 .. NA: they read the staged pixels)
-  // Claims are one LDS atomic (ctl[8]); the wave whose unit is the last one done (ctl[9])
-  // seeds the running maximum from the probe sums and arms the slot.  The patch that goes
-  // into a slot was claimed from the global queue -- and its PatchParams fetched -- while
-  // the previous patch of the slot was still running (ctl[18 ..]), so nothing of an
-  // opening waits for a global round trip except unit 0's own table loads.
-  constexpr int kProbeUnits = 4;
-  auto n_stage_units = [&]() {
-    const int n_max = max(Py * NCA, Qy * ((Qx + 15) / 16));
-    return (n_max + 64 * kStageBatch - 1) / (64 * kStageBatch);
-  };
-  // (lane 0) claims the patch after next for the bound slot and parks its parameters
-  auto prefetch_next = [&](const int first) {
-    int nb = first;
-    if (nb < 0) {
-      if (lane == 0) nb = 2 * static_cast<int>(gridDim.x) + atomicAdd(a.work_counter, 1);
-      nb = __builtin_amdgcn_readfirstlane(nb);
-    }
-    if (nb < n_items) {
-      const PatchParams pp = a.pp[nb];
-      if (lane == 0) {
-        ctl[19] = pp.y0[0]; ctl[20] = pp.x0[0]; ctl[21] = pp.c[0];
-        ctl[22] = pp.y0[1]; ctl[23] = pp.x0[1]; ctl[24] = pp.c[1];
-        ctl[25] = __float_as_int(pp.mu[0]); ctl[26] = __float_as_int(pp.mu[1]);
-      }
-    }
-    if (lane == 0) ctl[18] = nb;
-  };
-  auto open_unit_done = [&]() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    int dn = 0;
-    if (lane == 0) dn = atomicAdd(&ctl[9], 1) + 1;
-    dn = __builtin_amdgcn_readfirstlane(dn);
-    if (dn == __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[10]))) {
-      // the last unit: seed, then arm (generation + 1, tile 0; every LDS write of the
-      // opening is older than this one)
-      if (__builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[11]))) seed_finish();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (lane == 0) {
-        const int gen = (*const_cast<volatile int*>(&ctl[0]) >> 8) + 1;
-        *const_cast<volatile int*>(&ctl[0]) = gen << 8;
-      }
-    }
-  };
-  // unit c >= 1 of the bound slot's opening (claimed by the caller)
-  auto open_unit = [&](const int c) {
-    const int na = n_stage_units();
-    if (c <= na) {
-      const int y0a = __builtin_amdgcn_readfirstlane(ctl[12]), x0a = __builtin_amdgcn_readfirstlane(ctl[13]);
-      const int cca = __builtin_amdgcn_readfirstlane(ctl[14]);
-      const int y0b = __builtin_amdgcn_readfirstlane(ctl[15]), x0b = __builtin_amdgcn_readfirstlane(ctl[16]);
-      const int ccb = __builtin_amdgcn_readfirstlane(ctl[17]);
-      const StagePlane sa = {a.img[0], bytes0, a.ishape[0][1], y0a, x0a, Py, Px,
-                             cca, A_lds, a.pa, kPadTop, 0, NCA};
-      const StagePlane sb = {a.img[1], bytes1, a.ishape[1][1], y0b, x0b, Qy, Qx,
-                             ccb, B_lds, a.pb, 0, a.ml, (Qx + 15) / 16};
-      stage_patches<64>(sa, sb, lane, (c - 1) * 64 * kStageBatch, c * 64 * kStageBatch);
-      TICK(15)
-    } else {
-      // (the pixels and the zeroed sums first)
-      while (__builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[9])) < na + 1)
-        __builtin_amdgcn_s_sleep(2);
-      seed_probe(c - na - 1, kProbeUnits, 2);
-      TICK(16)
-    }
-    open_unit_done();
-  };
-  // the closer (or, at start-up, the wave that owns the slot): next patch into the bound slot
-  auto open_begin = [&]() {
-    const int nb = __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[18]));
-    if (nb >= n_items) {
-      if (lane == 0) ctl[3] = 1;   // retired: the control word stays at "nothing to draw"
-      return false;
-    }
-#ifdef SFM_MFMA_TIMING
-    ++npat;
-#endif
-    const int na = n_stage_units();
-    if (lane == 0) {
-      ctl[2] = nb;
-      ctl[12] = ctl[19]; ctl[13] = ctl[20]; ctl[14] = ctl[21];
-      ctl[15] = ctl[22]; ctl[16] = ctl[23]; ctl[17] = ctl[24];
-      ctl[4] = ctl[25]; ctl[5] = ctl[26];
-      *pmax_lds = 0;
-      *hot_lds = 0;
-      // initial store requests: as in the other lazy modes (see there)
-      const int pt = *best_lds >> 8, gt = (a.guard + 15) >> 4;
-      const int lo_t = max(pt - gt, 0), hi_t = min(pt + gt, a.n_order - 1);
-      const int pv = *lz_prev;
-      lz[0] = (pv && !a.widen ? 0 : static_cast<int>(((2u << hi_t) - 1u) & ~((1u << lo_t) - 1u))) |
-              pv | (a.widen ? (pv << 1) | (pv >> 1) : 0);
-      lz[1] = lz[2] = lz[3] = 0;
-      if (lz_cq[1] >= lz_cq[0]) {
-        lz_cq[2] = lz_cq[0];
-        lz_cq[3] = lz_cq[1];
-      }
-      lz_cq[0] = NQ;
-      lz_cq[1] = -1;
-      int probe_on = 0;
-      if (a.prune) {
-        best_lds[1] = 0;
-        const int n_done = best_lds[3];
-        best_lds[3] = n_done + 1;
-        probe_on = (a.probe && (best_lds[2] > 0 || (n_done & 7) == 0)) ? 1 : 0;
-        best_lds[4] = probe_on;
-        best_lds[2] = 0;
-      }
-      ctl[1] = 0;
-      ctl[9] = 0;
-      ctl[10] = 1 + na + (probe_on ? kProbeUnits : 0);
-      ctl[11] = probe_on;
-      // (in order behind everything above: the staging units may start)
-      *const_cast<volatile int*>(&ctl[8]) = 1;
-    }
-    // unit 0
-    const float* aux = a.aux + (long long)nb * (4 * a.aux_n + 4);
-    constexpr int kAuxP = (4 * (16 * NCA + 1) + 63) / 64;   // (Py <= Px = 16 NCA)
-    float auxv[kAuxP], tbv[kBoundStride / 64];
+      int sm = max(max(probe_lds[lane], probe_lds[64 + lane]),
+                   max(probe_lds[128 + lane], probe_lds[192 + lane]));
 #pragma unroll
-    for (int k = 0; k < kAuxP; ++k) {
-      const int i = lane + 64 * k;
-      auxv[k] = i < 4 * a.aux_n ? aux[i] : 0.f;
-    }
-    const float ca_new = aux[4 * a.aux_n + 0], cb_new = aux[4 * a.aux_n + 1];
-#pragma unroll
-    for (int k = 0; k < kBoundStride / 64; ++k)
-      tbv[k] = a.tbound[(long long)nb * kBoundStride + lane + 64 * k];
-#ifndef SFM_NO_TOUCH
-    {
-      // the column-sum tables this patch's finishing tiles build their table rows from
-      const char* gt = reinterpret_cast<const char*>(a.c16 + nb * a.c16_stride);
-      const unsigned junk_off = static_cast<unsigned>(reinterpret_cast<unsigned long long>(
-          (__attribute__((address_space(3))) float*)touch_junk));
-      const int n_lines = (2 * ((Py >> 4) + 1) * Px + Py + 1 + 15) >> 4;
-      for (int k = lane; k < n_lines; k += 64) {
-        const char* src = gt + (size_t)k * 64;
-        unsigned saved_m0;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-            "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-            : "=&s"(saved_m0)
-            : "v"(src), "s"(junk_off)
-            : "memory");
-      }
-    }
-#endif
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pr_lds[lane + 64 * k] = 0;
-    if (lane < 32) lz_ks[lane] = 0;
-#pragma unroll
-    for (int k = 0; k < kAuxP; ++k) {
-      const int i = lane + 64 * k;
-      if (i < 4 * a.aux_n) R_lds[i] = auxv[k];
-    }
-#pragma unroll
-    for (int k = 0; k < kBoundStride / 64; ++k) tb_lds[lane + 64 * k] = tbv[k];
-    if (lane == 0) {
-      ctl[6] = __float_as_int(ca_new);
-      ctl[7] = __float_as_int(cb_new);
-    }
-    TICK(17)
-    open_unit_done();
-    return true;
+      for (int d = 32; d > 0; d >>= 1) sm = max(sm, __shfl_xor(sm, d, 64));
+      const float m_lo = __int2float_rd(sm) - tb_lds[kBoundCorr];
+      if (lane == 0 && m_lo > 0.f) atomicMax(pmax_lds, __float_as_int(m_lo));
   };
-  int cur = 0;   // kModePipe: the slot this wave is bound to
-  if constexpr (PIPE) {
-    // start-up: waves 0 and 1 own the first opening of slot 0 / 1, everybody helps
-    cur = wave & 1;
-    bind_slot(cur);
-    if (wave < 2) {
-      prefetch_next(2 * static_cast<int>(blockIdx.x) + wave);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (open_begin()) prefetch_next(-1);
-    }
-  }
-  // (kModePipe: ONE trip -- its tile loop runs across all patches of the workgroup)
-  for (int item = PIPE ? 0 : a.xcd_heads ? pull_item(a, n_items, &q_state, next_lds) : blockIdx.x;
-       PIPE ? item == 0 : item < n_items;
-       item = PIPE ? 1 : a.xcd_heads ? pull_item(a, n_items, &q_state, next_lds)
-                                      : next_patch(a, item, next_lds)) {
+  for (int item = blockIdx.x; item < n_items; item = next_patch(a, item, next_lds)) {
     int b = item;
     int plane0 = a.plane[0], plane1 = a.plane[1];
     if (RAW && a.list) {
@@ -3130,8 +2809,6 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
 #endif
     TICK(7)
     float const_a = 0.f, const_b = 0.f;
-    float mua = 0.f, mub = 0.f, muab = 0.f;
-    if constexpr (!PIPE) {
     __syncthreads();  // previous patch fully consumed / zero fill done
     TICK(0)
     const PatchParams pp = a.pp[b];
@@ -3186,11 +2863,10 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
         // two tiles, whose bands are four tiles)
         const int pt = *best_lds >> 8, gt = (a.guard + 15) >> 4;
         const int lo_t = max(pt - gt, 0), hi_t = min(pt + gt, a.n_order - 1);
-        const int pv = *lz_prev;   // (widened by a tile: a store costs less than a recomputation)
+        const int pv = *lz_prev;
         // (the band of the peak tile only while there is no previous need mask: the
         // mask counts the guard band in rows and is usually a tile narrower)
-        lz[0] = (pv && !a.widen ? 0 : static_cast<int>(((2u << hi_t) - 1u) & ~((1u << lo_t) - 1u))) |
-                pv | (a.widen ? (pv << 1) | (pv >> 1) : 0);
+        lz[0] = (pv ? 0 : static_cast<int>(((2u << hi_t) - 1u) & ~((1u << lo_t) - 1u))) | pv;
         lz[1] = lz[2] = lz[3] = 0;
         if (lz_cq[1] >= lz_cq[0]) {   // (the previous patch had hot elements)
           lz_cq[2] = lz_cq[0];
@@ -3227,12 +2903,11 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
     __syncthreads();
 
     if (SAME && a.prune && a.probe && __builtin_amdgcn_readfirstlane(best_lds[4]))
-      seed_probe(wave, kWaves, 0);
+      seed_probe(wave, kWaves);
 
     TICK(1)
-    mua = pp.mu[0];
-    mub = pp.mu[1];
-    muab = mua * mub;
+    const float mua = pp.mu[0], mub = pp.mu[1];
+    float muab = mua * mub;
     asm volatile("" : "+v"(muab));  // every global load so far has been consumed
 #ifndef SFM_NO_TOUCH
     if (SAME) {
@@ -3287,10 +2962,9 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
       }
     }
 #endif
-    }  // !PIPE: the patch's staging
     const int* IA = (SAME || RAW) ? nullptr : a.integ[0] + b * a.integ_stride[0];
     const int* IB = (SAME || RAW) ? nullptr : a.integ[1] + b * a.integ_stride[1];
-    const float* G = SAME ? a.gtab + (long long)b * Py * Px : nullptr;   // (kModePipe: per draw)
+    const float* G = SAME ? a.gtab + (long long)b * Py * Px : nullptr;
     float* surf = a.surface + b * a.s_stride;
 
 #if SFM_DYNAMIC_TILES
@@ -3298,68 +2972,7 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
     for (;;) {
       int ti = 0, p = 0;
       bool forced = false;
-      if (PIPE && !redo_phase) {
-        // A tile of either slot.  The control word is tested with a plain read and drawn
-        // from with ONE atomic; the patch header is read in the same round (it cannot
-        // change while this wave holds a tile of the patch).
-        bool got = false;
-        for (int spin = 0;; ++spin) {
-          const int v = __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[0]));
-          const int dead_here = __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[3]));
-          // (the first tiles of a patch run against the seed of the running maximum alone:
-          // only pipe_admit of them are handed out before one is done)
-          const int done_here = __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[1]));
-          if ((v & 255) < a.n_order && ((v & 255) < a.pipe_admit || done_here > 0)) {
-            int v2 = 0, hb = 0, h4 = 0, h5 = 0, h6 = 0, h7 = 0;
-            if (lane == 0) v2 = atomicAdd(&ctl[0], 1);
-            hb = *const_cast<volatile int*>(&ctl[2]);
-            h4 = *const_cast<volatile int*>(&ctl[4]);
-            h5 = *const_cast<volatile int*>(&ctl[5]);
-            h6 = *const_cast<volatile int*>(&ctl[6]);
-            h7 = *const_cast<volatile int*>(&ctl[7]);
-            v2 = __builtin_amdgcn_readfirstlane(v2);
-            if ((v2 & 255) < a.n_order) {
-              ti = v2 & 255;
-              b = __builtin_amdgcn_readfirstlane(hb);
-              mua = __int_as_float(__builtin_amdgcn_readfirstlane(h4));
-              mub = __int_as_float(__builtin_amdgcn_readfirstlane(h5));
-              const_a = __int_as_float(__builtin_amdgcn_readfirstlane(h6));
-              const_b = __int_as_float(__builtin_amdgcn_readfirstlane(h7));
-              muab = mua * mub;
-              G = a.gtab + (long long)b * Py * Px;
-              surf = a.surface + b * a.s_stride;
-              got = true;
-              break;
-            }
-          }
-          // no tile here: a unit of this slot's opening, if it is being opened
-          {
-            const int u = __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[8]));
-            const int nu = __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[10]));
-            if (u >= 1 && u < nu) {
-              int c = 0;
-              if (lane == 0) c = atomicAdd(&ctl[8], 1);
-              c = __builtin_amdgcn_readfirstlane(c);
-              if (c < nu) {
-                TICK(13)
-                open_unit(c);
-                spin = 0;
-                continue;   // (same slot: more units, or its first tiles)
-              }
-            }
-          }
-          cur ^= 1;
-          bind_slot(cur);
-          if (dead_here &&
-              __builtin_amdgcn_readfirstlane(*const_cast<volatile int*>(&ctl[3])))
-            break;   // both slots retired: this wave is done
-          if (spin & 1) __builtin_amdgcn_s_sleep(4);
-        }
-        TICK(13)   // (timing build) looking for a tile
-        if (!got) break;
-        p = __builtin_amdgcn_readfirstlane(a.order[ti]);
-      }
-      if (!PIPE && !redo_phase) {
+      if (!redo_phase) {
         if (lane == 0) ti = atomicAdd(pmax_lds + 3, 1);
         ti = __builtin_amdgcn_readfirstlane(ti);
         if (ti >= a.n_order) {
@@ -3410,21 +3023,6 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
         int todo = need & done & (~*const_cast<volatile int*>(&lz[2]) | bad) &
                    ~*const_cast<volatile int*>(&lz[3]);
         todo = __builtin_amdgcn_readfirstlane(todo);
-        if (PIPE && todo == 0) {
-          // the patch is complete: publish it (what the peak kernels read), then put the
-          // next patch into this slot
-          if (lane == 0) {
-            a.v1[b] = __int_as_float(*const_cast<volatile int*>(pmax_lds));
-            a.hot_count[b] = *const_cast<volatile int*>(hot_lds);
-            a.skipmask[b] = ~*const_cast<volatile int*>(&lz[2]) &
-                            static_cast<int>((2u << (a.n_order - 1)) - 1u);
-          }
-          TICK(14)   // (timing build) end-of-patch pass of the closer
-          if (open_begin()) prefetch_next(-1);
-          TICK(17)
-          redo_phase = false;
-          continue;
-        }
         if (todo == 0) break;
         p = __builtin_ctz(todo);
         int old = 0;
@@ -3440,8 +3038,8 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
       constexpr bool forced = false;
       static_assert(!LAZY, "lazy stores need the dynamic tile queue");
 #endif
-      // (the tile's body is a block of its own: a `continue` inside it ends the tile and
-      // falls through to the completion count of kModePipe behind it)
+      // (the tile's body is a block of its own: a `continue` inside it ends the tile; the
+      // same code without the block gets another block layout and register allocation)
       do {
       // The two workgroups of a CU share each SIMD's MFMA pipe, and the issue
       // arbiter always favours the older wave: the younger workgroup would
@@ -4863,20 +4461,9 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
       }
       TICK(4)
       } while (0);
-      if constexpr (PIPE) {
-        TICK(9)   // (timing build) tiles that end without an epilogue
-        if (!forced) {
-          // done with this tile, whatever became of it; the wave that completes the
-          // patch closes it (every LDS write of this wave is older than the count)
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          int dn = 0;
-          if (lane == 0) dn = atomicAdd(&ctl[1], 1) + 1;
-          if (__builtin_amdgcn_readfirstlane(dn) == a.n_order) redo_phase = true;
-        }
-      }
     }
     TICK(5)
-    if (!PIPE && a.do_peaks) {
+    if (a.do_peaks) {
       // Publish the running maximum and the hot-list fill; the first-peak
       // search over them is mfma_first_peak_kernel (every patch in parallel,
       // off the matrix pipeline's critical path).
@@ -4919,14 +4506,7 @@ __global__ void __launch_bounds__(MODE == kModePipe ? 2 * kThreads
            wall ? cyc * 100 / wall : 0, tph[2] / (npat ? npat : 1),
            tph[3] / (npat ? npat : 1));
   }
-  if (PIPE && blockIdx.x == 7 && lane == 0) {
-    // totals of this wave over the launch (cycles): divide by the workgroup's patches
-    printf("pipewave %d opened %d tiles %d: total %lld seek %lld setup %lld tests %lld groups %lld loop-tail %lld "
-           "epi %lld hot %lld exit %lld close %lld stage %lld probe %lld arm %lld\n",
-           wave, npat, tiles_drawn, clock64() - cstart, tph[13], tph[10], tph[11], tph[12], tph[2], tph[3],
-           tph[4], tph[9], tph[14], tph[15], tph[16], tph[17]);
-  }
-  if (!PIPE && blockIdx.x == 7 && lane == 0)
+  if (blockIdx.x == 7 && lane == 0)
     printf("wave %d patches %d: next %lld sync %lld pix %lld aux+touch %lld stagesync %lld mfma %lld (+ setup %lld tests %lld groups %lld) epi %lld hot %lld tail %lld peaks %lld\n",
            wave, npat, tph[7] / npat, tph[0] / npat, tph[8] / npat, tph[9] / npat, tph[1] / npat, tph[2] / npat,
            tph[10] / npat, tph[11] / npat, tph[12] / npat, tph[3] / npat,
@@ -5020,7 +4600,7 @@ Ws carve_ws(const SfmXcorrDesc* d, void* base) {
   std::memset(&w, 0, sizeof(w));
   const size_t B = d->batch;
   w.pp = c.take<PatchParams>(B);
-  w.counter = c.take<int>(64 + kXcds * kHeadPitch);  // queue head, clk probe, per-XCD heads
+  w.counter = c.take<int>(64);  // queue head, clk probe
   if (same_size(d)) {
     w.aux_n = std::max(d->patch[1], d->patch[2]) + 1;
     w.gtab = c.take<float>(B * d->patch[1] * d->patch[2]);
@@ -5041,31 +4621,6 @@ Ws carve_ws(const SfmXcorrDesc* d, void* base) {
 }
 
 int device_cus();
-
-// kModePipe: one workgroup of eight waves per CU, two patch slots in LDS.
-template <int NCA, int NCE>
-int launch_pipe(const MfmaArgs& a, int grid, hipStream_t st) {
-  const size_t lds = 2 * static_cast<size_t>(a.slot_bytes);
-  static size_t attr_set = 0;
-  if (lds > attr_set) {
-    SFM_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&xcorr_mfma_kernel<NCA, NCE, kModePipe>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    attr_set = lds;
-  }
-  grid = std::min((grid + 1) / 2, device_cus());
-  {
-    const char* g = sfm::option("SFM_MFMA_GRID");   // (tests: many patches per workgroup)
-    if (g && std::atoi(g) > 0) grid = std::min(grid, std::max(1, std::atoi(g) / 2));
-  }
-  sfm::prof_begin(sfm::kProfXcorr, st);
-  hipLaunchKernelGGL((xcorr_mfma_kernel<NCA, NCE, kModePipe>), dim3(grid),
-                     dim3(2 * kThreads), lds, st, a);
-  sfm::prof_end(sfm::kProfXcorr, st);
-  sfm::prof_clock(sfm::kProfXcorr, a.clk, st, 5);
-  SFM_LAUNCH_CHECK();
-  return SFM_OK;
-}
 
 template <int NCA, int NCE, int MODE>
 int launch_one(const MfmaArgs& a, int grid, size_t lds, hipStream_t st) {
@@ -5128,13 +4683,6 @@ int launch_variant(const MfmaArgs& a, int mode, int grid, size_t lds,
     case kModeSameLazy: return launch_one<NCA, NCE, kModeSameLazy>(a, grid, lds, st);
     case kModeSameExactLazy: return launch_one<NCA, NCE, kModeSameExactLazy>(a, grid, lds, st);
     case kModeSameExactLazyG: return launch_one<NCA, NCE, kModeSameExactLazyG>(a, grid, lds, st);
-    case kModePipe:
-      // (instantiated for the 160-wide variant; the narrower ones keep three or four
-      // workgroups per CU and are not priced by the per-patch phases)
-      if constexpr (NCA == 10)
-        return launch_pipe<NCA, NCE>(a, grid, st);
-      else
-        return launch_one<NCA, NCE, kModeSameExactLazyG>(a, grid, lds, st);
     case kModeRaw: return launch_one<NCA, NCE, kModeRaw>(a, grid, lds, st);
     default: return launch_one<NCA, NCE, kModeGeneral>(a, grid, lds, st);
   }
@@ -5361,12 +4909,6 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
   {
     const char* e = sfm::measure_option("SFM_MFMA_QUEUE");
     a.work_counter = (e && e[0] == '0') ? nullptr : w.counter;
-    // Measured on MI355X (8192^2 warped pair, A/B on one box, pruned and not):
-    // 15.48-15.53 / 20.0-20.06 ms either way -- the staging round trip is hidden
-    // behind the other workgroup's matrix phase, the kernel is matrix-pipe / power
-    // bound, so L2 locality of the pixel loads buys nothing.  Opt-in ("1").
-    const char* x = sfm::option("SFM_MFMA_XCD");
-    a.xcd_heads = (a.work_counter && x && x[0] == '1') ? w.counter + 64 : nullptr;
     a.clk = reinterpret_cast<long long*>(w.counter + 16);
     const char* p = sfm::measure_option("SFM_MFMA_PRIO");
     a.prio_mode = p ? std::atoi(p) : 0;
@@ -5409,14 +4951,6 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
       // lazy modes ("0": no tests); each test schedules the next, see check_after
       const char* e = sfm::option("SFM_MFMA_EARLY");
       a.early = e ? std::atoi(e) : 1;
-      // initial store requests of a patch: what the previous patch of the workgroup
-      // needed, "1": widened by a row tile on either side.  (Before the in-loop test
-      // a spare request cost a store and saved a recomputation when the peak moved
-      // to the next tile; now a requested tile also runs its whole row loop where
-      // an unrequested one is abandoned after ~3/4 of it.  Measured on the 8192^2
-      // warped pair: 12.29 ms per launch without, 12.54 ms with the widening.)
-      const char* wd = sfm::option("SFM_MFMA_WIDEN");
-      a.widen = wd ? std::atoi(wd) : 0;
       const char* ta = sfm::measure_option("SFM_MFMA_TOUCH_ALL");
       a.touch_all = ta && ta[0] == '1';
       const char* nw = sfm::option("SFM_MFMA_NARROW");
@@ -5479,7 +5013,7 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
                                         static_cast<int>(prep_lds)));
       prep_gen_attr = prep_lds;
     }
-    if (kVariants[vi].nca > 10 && a.P[1] <= 512 && !a.xcd_heads) {
+    if (kVariants[vi].nca > 10 && a.P[1] <= 512) {
       // search-window variants: the wide prep pass (see mfma_prep_wide_kernel)
       const size_t wide_lds = (size_t)a.P[0] * (16 * ((a.P[1] + 15) / 16) + 16);
       static size_t wide_attr = 0;
@@ -5497,23 +5031,9 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
   }
   SFM_LAUNCH_CHECK();
   const size_t lds = (size_t)l.a_bytes + l.b_bytes + r_bytes + 16 + 4 * kBoundStride + 48 + 128 + 160 + 128;
-  a.slot_bytes = static_cast<int>((lds + 4 * kPipeCtl + 4 * 256 + 15) / 16 * 16);
   const int grid = d->batch;  // capped to the resident workgroups in launch_one
-  // cross-patch pipeline (kModePipe): SFM_MFMA_PIPE=1
-  bool pipe = false;
-  {
-    const char* e = sfm::option("SFM_MFMA_PIPE");
-    pipe = e && e[0] == '1' && a.lazy_g && kVariants[vi].nca == 10 && a.work_counter &&
-           !a.xcd_heads && a.P[0] <= a.P[1] && a.n_order < 128 &&
-           2 * (size_t)a.slot_bytes + 2048 <= 160 * 1024;
-  }
-  {
-    const char* e = sfm::option("SFM_MFMA_PIPE_ADMIT");
-    a.pipe_admit = e && std::atoi(e) > 0 ? std::atoi(e) : 2;
-  }
   const int mode = !same ? kModeGeneral
-                   : exact ? (pipe ? kModePipe
-                              : a.lazy_g ? kModeSameExactLazyG
+                   : exact ? (a.lazy_g ? kModeSameExactLazyG
                                        : lazy ? kModeSameExactLazy : kModeSameExact)
                            : (lazy ? kModeSameLazy : kModeSame);
   if (int rc = launch_mode(vi, a, mode, grid, lds, st)) return rc;

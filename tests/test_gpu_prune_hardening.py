@@ -150,16 +150,13 @@ def test_prep_without_staging_matches_the_staged_form(gpu, py, px, mean):
 
 
 @pytest.mark.parametrize('mean', [None, 100.0])
-def test_cross_patch_pipeline_is_bit_identical(gpu, mean):
-  """SFM_MFMA_PIPE=1 (kModePipe: one workgroup of eight waves per CU, two patch
-  slots in LDS, the tile queue running across the patch boundary, the closing wave
-  recomputing / publishing / re-opening alone, openings cut into units any idle wave
-  takes) against the two-workgroup kernel and the un-pruned run: the same bits on the
-  batch that interleaves all seven adversarial image kinds, through 1, 3 and all
-  workgroups (1 workgroup = both slots of ONE CU carry the whole batch: every slot
-  hand-over, retirement with tiles still in flight in the other slot, batches of 1
-  and 2 patches = a slot that never opens), with every admission limit and with the
-  kernel's other switches on top."""
+def test_interleaved_batches_through_few_workgroups_are_bit_identical(gpu, mean):
+  """The production kernel on the batch that interleaves all seven adversarial
+  image kinds, run through 2, 6 and all workgroups (a few workgroups carry the
+  state of many patches from one to the next: previous need mask, hot columns,
+  seed block), with its in-loop switches off one at a time and on three other peak
+  geometries: the same bits as the default launch and the un-pruned run.  Batches
+  of 1, 2 and 3 patches leave workgroups without a patch."""
   from sofima_amd import _abi, flow_field
   pre, post = _mosaic(53)
   rng = np.random.default_rng(17)
@@ -173,49 +170,32 @@ def test_cross_patch_pipeline_is_bit_identical(gpu, mean):
     if b == 98:
       with _abi.option('SFM_MFMA_PRUNE', 0):
         np.testing.assert_array_equal(flow_field.batched_xcorr_peaks(*args, method=2, **kw), ref)
-    with _abi.option('SFM_MFMA_PIPE', 1):
-      for grid in (0, 2, 6):
-        with _abi.option('SFM_MFMA_GRID', grid):
-          for admit in ((255, 2, 1) if b == 98 else (0,)):
-            with _abi.option('SFM_MFMA_PIPE_ADMIT', admit):
-              np.testing.assert_array_equal(
-                  flow_field.batched_xcorr_peaks(*args, method=2, **kw), ref,
-                  err_msg=f'batch {b} grid {grid} admit {admit}')
-      if b == 98:
-        for name, val in (('SFM_MFMA_EARLY', 0), ('SFM_MFMA_NARROW', 0), ('SFM_MFMA_PROBE', 0),
-                          ('SFM_MFMA_WIDEN', 1)):
-          with _abi.option(name, val), _abi.option('SFM_MFMA_GRID', 2):
-            np.testing.assert_array_equal(
-                flow_field.batched_xcorr_peaks(*args, method=2, **kw), ref,
-                err_msg=f'{name}={val}')
-  # other peak geometries (guard bands of 60 rows: the closer recomputes band tiles)
+    for grid in (0, 2, 6):
+      with _abi.option('SFM_MFMA_GRID', grid):
+        np.testing.assert_array_equal(
+            flow_field.batched_xcorr_peaks(*args, method=2, **kw), ref,
+            err_msg=f'batch {b} grid {grid}')
+    if b == 98:
+      for name, val in (('SFM_MFMA_EARLY', 0), ('SFM_MFMA_NARROW', 0), ('SFM_MFMA_PROBE', 0)):
+        with _abi.option(name, val), _abi.option('SFM_MFMA_GRID', 2):
+          np.testing.assert_array_equal(
+              flow_field.batched_xcorr_peaks(*args, method=2, **kw), ref,
+              err_msg=f'{name}={val}')
+  # other peak geometries (guard bands of 60 rows: band tiles are recomputed)
   starts, _ = _interleaved_starts(rng, 70, py, px)
   for radius, md, thr in ((30, 2, 0.9), (5, 2, 0.2), (12, 6, 0.5)):
     kw = dict(min_distance=md, threshold_rel=thr, peak_radius=radius,
               post_patch_size=(py, px), post_starts=starts)
     args = (pre, post, None, None, (py, px), starts, mean)
     ref = flow_field.batched_xcorr_peaks(*args, method=2, **kw)
-    with _abi.option('SFM_MFMA_PIPE', 1), _abi.option('SFM_MFMA_GRID', 4):
+    with _abi.option('SFM_MFMA_GRID', 4):
       np.testing.assert_array_equal(flow_field.batched_xcorr_peaks(*args, method=2, **kw), ref)
-
-
-def test_cross_patch_pipeline_whole_bench_field(gpu):
-  """The literal bench pair through the pipeline kernel: the whole [4, 201, 201]
-  field equals the production kernel's (which the oracle test above pins)."""
-  import bench
-  from sofima_amd import _abi, flow_field as ff
-  pre, post = bench.synth_pair(8192, 1002, warp=bench.WARP)
-  calc = ff.JAXMaskedXCorrWithStatsCalculator()
-  ref = calc.flow_field(pre, post, bench.PATCH, bench.STEP, batch_size=bench.BATCH)
-  with _abi.option('SFM_MFMA_PIPE', 1):
-    got = calc.flow_field(pre, post, bench.PATCH, bench.STEP, batch_size=bench.BATCH)
-  np.testing.assert_array_equal(got, ref)
 
 
 def test_every_kernel_switch_returns_the_same_bits(gpu):
   """The run-time switches of the correlation kernel select schedules, never
   results: PROBE, TOUCH_ALL, EXACT, QUEUE, PRIO, MAX_WG_PER_CU (measurement
-  switches) next to PRUNE / LAZY / EARLY / WIDEN / NARROW / XCD / GRID."""
+  switches) next to PRUNE / LAZY / LAZYG / EARLY / NARROW / GRID."""
   from sofima_amd import _abi, flow_field
   pre, post = _mosaic(43)
   rng = np.random.default_rng(9)
@@ -235,9 +215,8 @@ def test_every_kernel_switch_returns_the_same_bits(gpu):
       measure = ()
     for name, values in measure + (
                          ('SFM_MFMA_PRUNE', (0,)), ('SFM_MFMA_LAZY', (0,)), ('SFM_MFMA_LAZYG', (0,)),
-                         ('SFM_MFMA_EARLY', (0, 1, 4)), ('SFM_MFMA_WIDEN', (1,)),
-                         ('SFM_MFMA_NARROW', (0, 4)), ('SFM_MFMA_XCD', (1,)),
-                         ('SFM_MFMA_GRID', (1, 3)), ('SFM_MFMA_PIPE', (1,))):
+                         ('SFM_MFMA_EARLY', (0, 1, 4)), ('SFM_MFMA_NARROW', (0, 4)),
+                         ('SFM_MFMA_GRID', (1, 3))):
       for v in values:
         with _abi.option(name, v):
           got = flow_field.batched_xcorr_peaks(*args, method=2, **kw)
