@@ -317,6 +317,48 @@ typedef struct SfmCleanFlowDesc {
 int sfm_clean_flow(const SfmCleanFlowDesc* desc, float* out);
 
 /* ------------------------------------------------------------------------
+ * Flow reconciliation, the step between clean-up and mesh relaxation.
+ * Replaces flow_utils.reconcile_flows (flow_utils.py:81-135): flows 1..K-1
+ * fill (all channels) where the merged channel 0 is NaN (3 channels: and
+ * |dz| >= min_delta_z); then, each only when its threshold is > 0, vectors are
+ * invalidated (all channels NaN) where the zero-padded x / y differences of
+ * channel 0 / 1 exceed max_gradient, where channel 0 or 1 deviates from the
+ * 3 x 3 median of the nan_to_num'ed field (per z slice, mode "reflect") by
+ * more than max_deviation, and where the 4-connected component of valid
+ * (NaN-free) vectors in its z slice has fewer than min_patch_size vectors.
+ * As in the reference, the invalid vectors of a slice count as one more
+ * component: when there are fewer than min_patch_size of them they become
+ * all-NaN too.  Bit-exact: values are only copied, subtracted or compared.
+ * The gradient differences are taken in double (np.diff's zero padding
+ * promotes the field to float64) and compared with max_gradient in double.
+ * The float32 deviations and |dz| are compared with max_deviation /
+ * min_delta_z in double: to compare in float32, as NumPy does with a Python
+ * number, pass the threshold rounded to float32.  At most 2^31 - 1 vectors
+ * (int32 indices); out must not overlap flows.
+ * ---------------------------------------------------------------------- */
+typedef struct SfmReconcileDesc {
+  int32_t channels;             /* 2 or 3                                    */
+  int32_t shape[3];             /* z, y, x                                   */
+  int32_t num_flows;            /* K >= 1                                    */
+  double max_gradient;          /* <= 0: not applied                         */
+  double max_deviation;         /* <= 0: not applied                         */
+  double min_delta_z;           /* 3 channels only                           */
+  int64_t min_patch_size;       /* <= 0: not applied                         */
+  const float* flows;           /* device [K, channels, z, y, x], packed, in
+                                   order of decreasing preference            */
+  void* workspace;              /* sfm_reconcile_flows_workspace_bytes()     */
+  size_t workspace_bytes;
+  void* stream;
+} SfmReconcileDesc;
+
+/* Host arithmetic only (callable without a GPU); 0 for a NULL descriptor or
+ * an empty shape. */
+size_t sfm_reconcile_flows_workspace_bytes(const SfmReconcileDesc* desc);
+/* out: device float [channels, z, y, x].  SFM_ERR_WORKSPACE when the
+ * workspace is missing or too small. */
+int sfm_reconcile_flows(const SfmReconcileDesc* desc, float* out);
+
+/* ------------------------------------------------------------------------
  * Fold / stretch detection on a relaxed mesh, the step after relaxation.
  * Replaces map_utils.mask_irregular (map_utils.py:737-786): a node is bad when
  * the distance to its +x (+y) neighbour leaves [frac, max_frac] * stride; the

@@ -118,6 +118,22 @@ class SfmCleanFlowDesc(C.Structure):
   ]
 
 
+class SfmReconcileDesc(C.Structure):
+  _fields_ = [
+      ('channels', i32),
+      ('shape', i32 * 3),
+      ('num_flows', i32),
+      ('max_gradient', C.c_double),
+      ('max_deviation', C.c_double),
+      ('min_delta_z', C.c_double),
+      ('min_patch_size', C.c_int64),
+      ('flows', C.c_void_p),
+      ('workspace', C.c_void_p),
+      ('workspace_bytes', C.c_size_t),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmMaskIrregularDesc(C.Structure):
   _fields_ = [
       ('shape', i32 * 2),
@@ -363,6 +379,8 @@ SIGNATURES = {
     'sfm_peaks': (C.c_int, [C.POINTER(SfmPeaksDesc), C.c_void_p]),
     'sfm_compose_maps': (C.c_int, [C.POINTER(SfmComposeDesc), C.c_void_p]),
     'sfm_clean_flow': (C.c_int, [C.POINTER(SfmCleanFlowDesc), C.c_void_p]),
+    'sfm_reconcile_flows_workspace_bytes': (C.c_size_t, [C.POINTER(SfmReconcileDesc)]),
+    'sfm_reconcile_flows': (C.c_int, [C.POINTER(SfmReconcileDesc), C.c_void_p]),
     'sfm_mask_irregular': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,
                                      C.c_void_p]),
     'sfm_flow_starts': (C.c_int, [C.POINTER(SfmFlowStartsDesc)]),

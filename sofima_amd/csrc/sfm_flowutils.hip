@@ -456,3 +456,316 @@ extern "C" int sfm_clean_flow(const SfmCleanFlowDesc* d, float* out) {
   SFM_LAUNCH_CHECK();
   return SFM_OK;
 }
+
+// ---------------------------------------------------------------------------
+// flow_utils.reconcile_flows (flow_utils.py:81-135):
+//
+//   1. merge + gradient: one thread per vector; the merged ch0 / ch1 of the
+//      x / y neighbours the gradient needs are merged again by the reading
+//      thread (K loads each), so nothing is exchanged between threads;
+//   2. 3 x 3 median deviation (same window code as clean_flow, always 2-D);
+//   3. small components, per z slice, 4-connected: union-find on int32 vector
+//      indices (Playne & Hawick 2018).  Parents only ever point to smaller
+//      indices (hooks and path halving are atomicMin), so find and union
+//      terminate by construction; every parent access inside the union launch
+//      is an agent-scope atomic (per-XCD L2s are not coherent).  Then one pass
+//      compresses and counts component sizes at the roots and the invalid
+//      vectors per slice, and one pass masks.
+// Stage 2 reads a copy of stage 1's output (workspace); stage 3 works in place.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct ReconcileArgs {
+  const float* flows;  // [K, C, Z, Y, X]
+  const float* src;    // stage input [C, Z, Y, X]
+  float* dst;          // stage output [C, Z, Y, X]
+  int* parent;         // [N]; -1 = invalid vector
+  int* size;           // [N]; component size at the root
+  int* n0;             // [Z]; invalid vectors per slice
+  int K, C, Z, Y, X;
+  double max_grad, max_dev, min_dz;  // compared in double, see SfmReconcileDesc
+  long long min_patch;
+};
+
+// Channel `ch` of the merged flow at vector i: the first flow is taken, and a
+// later one replaces all channels wherever channel 0 is still NaN (and, for 3
+// channels, |dz| >= min_delta_z; NaN >= t is false).
+__device__ __forceinline__ float merged_at(const ReconcileArgs& a, long long n, long long i,
+                                          int ch) {
+  const long long fs = (long long)a.C * n;
+  float v0 = a.flows[i];
+  float v = a.flows[ch * n + i];
+  for (int k = 1; k < a.K; ++k) {
+    const float* f = a.flows + k * fs;
+    if (isnan(v0) && (a.C != 3 || static_cast<double>(fabsf(f[2 * n + i])) >= a.min_dz)) {
+      v0 = f[i];
+      v = f[ch * n + i];
+    }
+  }
+  return v;
+}
+
+__global__ void __launch_bounds__(kBlock) reconcile_merge_kernel(ReconcileArgs a) {
+  const long long n = (long long)a.Z * a.Y * a.X;
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  float v[3];
+  for (int c = 0; c < a.C; ++c) v[c] = merged_at(a, n, i, c);
+  bool bad = false;
+  if (a.max_grad > 0.0) {
+    // np.diff with prepend=0 / append=0: the int64 zero promotes the field to
+    // float64, so the differences are taken in double; a missing neighbour is 0;
+    // |a-b| > t is false for a NaN difference
+    const int x = static_cast<int>(i % a.X);
+    const int y = static_cast<int>((i / a.X) % a.Y);
+    const float l = x > 0 ? merged_at(a, n, i - 1, 0) : 0.f;
+    const float r = x + 1 < a.X ? merged_at(a, n, i + 1, 0) : 0.f;
+    const float u = y > 0 ? merged_at(a, n, i - a.X, 1) : 0.f;
+    const float d = y + 1 < a.Y ? merged_at(a, n, i + a.X, 1) : 0.f;
+    const double c0 = v[0], c1 = v[1];
+    bad = fabs(c0 - static_cast<double>(l)) > a.max_grad ||
+          fabs(static_cast<double>(r) - c0) > a.max_grad ||
+          fabs(c1 - static_cast<double>(u)) > a.max_grad ||
+          fabs(static_cast<double>(d) - c1) > a.max_grad;
+  }
+  for (int c = 0; c < a.C; ++c) a.dst[c * n + i] = bad ? NAN : v[c];
+}
+
+// Median of the 3 x 3 window of nan_to_num(comp) in one z slice (reflect).
+__device__ float median9(const float* comp, const ReconcileArgs& a, int z, int y, int x) {
+  float w[9];
+  int n = 0;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int yy = reflect(y + dy, a.Y), xx = reflect(x + dx, a.X);
+      const float v = nan_to_num(comp[((long long)z * a.Y + yy) * a.X + xx]);
+      int k = n++;  // insertion sort
+      while (k > 0 && w[k - 1] > v) {
+        w[k] = w[k - 1];
+        --k;
+      }
+      w[k] = v;
+    }
+  return w[4];
+}
+
+__global__ void __launch_bounds__(kBlock) reconcile_median_kernel(ReconcileArgs a) {
+  const long long n = (long long)a.Z * a.Y * a.X;
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int x = static_cast<int>(i % a.X);
+  const int y = static_cast<int>((i / a.X) % a.Y);
+  const int z = static_cast<int>(i / ((long long)a.X * a.Y));
+  // np.max over channels 0 and 1 propagates NaN, and NaN > t is false
+  const float d0 = fabsf(median9(a.src, a, z, y, x) - a.src[i]);
+  const float d1 = fabsf(median9(a.src + n, a, z, y, x) - a.src[n + i]);
+  const bool bad =
+      !isnan(d0) && !isnan(d1) && static_cast<double>(fmaxf(d0, d1)) > a.max_dev;
+  for (int c = 0; c < a.C; ++c) a.dst[c * n + i] = bad ? NAN : a.src[c * n + i];
+}
+
+__device__ __forceinline__ int load_parent(const int* p, int i) {
+  return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int lower_parent(int* p, int i, int v) {
+  return __hip_atomic_fetch_min(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Root of i, halving the path on the way (p[i] <- p[p[i]], never upwards).
+__device__ int find_root(int* p, int i) {
+  while (true) {
+    const int q = load_parent(p, i);
+    if (q == i) return i;
+    const int g = load_parent(p, q);
+    if (g == q) return q;
+    lower_parent(p, i, g);
+    i = g;
+  }
+}
+
+// Hooks the larger root under the smaller; when the hook loses a race (the
+// larger root got a parent meanwhile) it retries from that parent.
+__device__ void unite(int* p, int a, int b) {
+  while (true) {
+    a = find_root(p, a);
+    b = find_root(p, b);
+    if (a == b) return;
+    if (a > b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = lower_parent(p, b, a);
+    if (old == b) return;
+    b = old;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) ccl_init_kernel(ReconcileArgs a) {
+  const long long n = (long long)a.Z * a.Y * a.X;
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  bool valid = true;
+  for (int c = 0; c < a.C; ++c) valid = valid && !isnan(a.dst[c * n + i]);
+  a.parent[i] = valid ? static_cast<int>(i) : -1;
+  a.size[i] = 0;
+}
+
+__global__ void __launch_bounds__(kBlock) ccl_union_kernel(ReconcileArgs a) {
+  const int n = a.Z * a.Y * a.X;  // <= INT32_MAX (checked by the entry point)
+  const long long il = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (il >= n) return;
+  const int i = static_cast<int>(il);
+  if (load_parent(a.parent, i) < 0) return;
+  const int x = i % a.X;
+  const int y = (i / a.X) % a.Y;
+  // right and down neighbours of the same slice: the cross structure
+  if (x + 1 < a.X && load_parent(a.parent, i + 1) >= 0) unite(a.parent, i, i + 1);
+  if (y + 1 < a.Y && load_parent(a.parent, i + a.X) >= 0) unite(a.parent, i, i + a.X);
+}
+
+// parent[i] <- root; component sizes at the roots; invalid vectors per slice.
+__global__ void __launch_bounds__(kBlock) ccl_count_kernel(ReconcileArgs a) {
+  __shared__ int bg[kBlock];  // invalid count per slice touched by this block
+  const long long n = (long long)a.Z * a.Y * a.X;
+  const long long plane = (long long)a.Y * a.X;
+  const long long first = blockIdx.x * (long long)kBlock;
+  const long long i = first + threadIdx.x;
+  const long long z0 = first / plane;
+  bg[threadIdx.x] = 0;
+  __syncthreads();
+  const bool in = i < n;
+  int r = -1;
+  if (in) {
+    r = a.parent[i];
+    if (r >= 0) {
+      // the tree is final: plain loads, and a stale entry is still an ancestor
+      int q = a.parent[r];
+      while (q != r) {
+        r = q;
+        q = a.parent[r];
+      }
+      a.parent[i] = r;
+    } else {
+      atomicAdd(&bg[i / plane - z0], 1);
+    }
+  }
+  // lanes of a wave mostly share a root: one add for those of the first lane
+  const bool act = r >= 0;
+  const unsigned long long actm = __ballot(act);
+  if (actm) {
+    const int leader = __ffsll(static_cast<long long>(actm)) - 1;
+    const int r0 = __shfl(r, leader);
+    const unsigned long long same = __ballot(act && r == r0);
+    if (static_cast<int>(__lane_id()) == leader) atomicAdd(&a.size[r0], __popcll(same));
+    if (act && r != r0) atomicAdd(&a.size[r], 1);
+  }
+  __syncthreads();
+  const long long last = (first + kBlock < n ? first + kBlock : n) - 1;
+  if (threadIdx.x <= last / plane - z0 && bg[threadIdx.x] > 0)
+    atomicAdd(&a.n0[z0 + threadIdx.x], bg[threadIdx.x]);
+}
+
+// np.unique counts the background label too: when 0 < n0 < min_patch_size the
+// invalid vectors of the slice become all-NaN as well.
+__global__ void __launch_bounds__(kBlock) ccl_mask_kernel(ReconcileArgs a) {
+  const long long n = (long long)a.Z * a.Y * a.X;
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int r = a.parent[i];
+  const long long cnt = r >= 0 ? a.size[r] : a.n0[i / ((long long)a.Y * a.X)];
+  if (cnt < a.min_patch)
+    for (int c = 0; c < a.C; ++c) a.dst[c * n + i] = NAN;
+}
+
+struct ReconcileLayout {
+  size_t copy, parent, size, n0, bytes;
+};
+
+ReconcileLayout reconcile_layout(const SfmReconcileDesc* d) {
+  const size_t n = (size_t)d->shape[0] * d->shape[1] * d->shape[2];
+  auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+  ReconcileLayout w{};
+  size_t off = 0;
+  if (d->max_deviation > 0.0) {
+    w.copy = off;
+    off += up((size_t)d->channels * n * sizeof(float));
+  }
+  if (d->min_patch_size > 0) {
+    w.parent = off;
+    off += up(n * sizeof(int));
+    w.size = off;
+    off += up(n * sizeof(int));
+    w.n0 = off;
+    off += up((size_t)d->shape[0] * sizeof(int));
+  }
+  w.bytes = off > 256 ? off : 256;
+  return w;
+}
+
+}  // namespace
+
+extern "C" size_t sfm_reconcile_flows_workspace_bytes(const SfmReconcileDesc* d) {
+  if (!d) return 0;
+  for (int i = 0; i < 3; ++i)
+    if (d->shape[i] < 1) return 0;
+  return reconcile_layout(d).bytes;
+}
+
+extern "C" int sfm_reconcile_flows(const SfmReconcileDesc* d, float* out) {
+  if (!d || !d->flows || !out)
+    return sfm::fail(SFM_ERR_INVALID, "reconcile_flows: NULL argument");
+  if (d->channels != 2 && d->channels != 3)
+    return sfm::fail(SFM_ERR_INVALID, "reconcile_flows: %d channels, need 2 or 3",
+                     d->channels);
+  if (d->num_flows < 1)
+    return sfm::fail(SFM_ERR_INVALID, "reconcile_flows: no flows");
+  for (int i = 0; i < 3; ++i)
+    if (d->shape[i] < 1) return sfm::fail(SFM_ERR_INVALID, "reconcile_flows: bad shape");
+  const long long n = (long long)d->shape[0] * d->shape[1] * d->shape[2];
+  if (n > 0x7fffffffLL)
+    return sfm::fail(SFM_ERR_INVALID, "reconcile_flows: %lld vectors exceed int32 indices", n);
+  const ReconcileLayout w = reconcile_layout(d);
+  if (!d->workspace || d->workspace_bytes < w.bytes)
+    return sfm::fail(SFM_ERR_WORKSPACE, "reconcile_flows workspace needs %zu bytes, got %zu",
+                     w.bytes, d->workspace_bytes);
+  char* ws = static_cast<char*>(d->workspace);
+  ReconcileArgs a{};
+  a.flows = d->flows;
+  a.K = d->num_flows;
+  a.C = d->channels;
+  a.Z = d->shape[0];
+  a.Y = d->shape[1];
+  a.X = d->shape[2];
+  a.max_grad = d->max_gradient;
+  a.max_dev = d->max_deviation;
+  a.min_dz = d->min_delta_z;
+  a.min_patch = d->min_patch_size;
+  const unsigned grid = static_cast<unsigned>((n + kBlock - 1) / kBlock);
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  const bool median = a.max_dev > 0.0;
+  float* copy = reinterpret_cast<float*>(ws + w.copy);
+  a.dst = median ? copy : out;
+  hipLaunchKernelGGL(reconcile_merge_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+  SFM_LAUNCH_CHECK();
+  if (median) {
+    a.src = copy;
+    a.dst = out;
+    hipLaunchKernelGGL(reconcile_median_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+    SFM_LAUNCH_CHECK();
+  }
+  if (a.min_patch > 0) {
+    a.dst = out;
+    a.parent = reinterpret_cast<int*>(ws + w.parent);
+    a.size = reinterpret_cast<int*>(ws + w.size);
+    a.n0 = reinterpret_cast<int*>(ws + w.n0);
+    SFM_HIP_CHECK(hipMemsetAsync(a.n0, 0, (size_t)a.Z * sizeof(int), st));
+    hipLaunchKernelGGL(ccl_init_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(ccl_union_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(ccl_count_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(ccl_mask_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+    SFM_LAUNCH_CHECK();
+  }
+  return SFM_OK;
+}

@@ -1,13 +1,14 @@
 """Flow-field clean-up on MI355X.
 
-Drop-in for `flow_utils.clean_flow` of the reference (flow_utils.py:37-78), the
-quality filter between flow estimation and mesh relaxation (SURVEY.md 8f,
-rank 2).  `reconcile_flows` and the other helpers of the reference's
-flow_utils.py are host-side post-processing and out of scope.
+Drop-ins for `flow_utils.clean_flow` (flow_utils.py:37-78), the quality
+filter between flow estimation and mesh relaxation, and
+`flow_utils.reconcile_flows` (flow_utils.py:81-135), which merges flows and
+filters them before the mesh solve.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -47,6 +48,76 @@ def clean_flow(flow, min_peak_ratio: float, min_peak_sharpness: float,
   d.stream = _dev.stream_ptr()
   out = torch.empty((dim,) + tuple(f.shape[1:]), dtype=torch.float32, device=dev)
   _abi.check(_abi.load().sfm_clean_flow(C.byref(d), out.data_ptr()))
+  return DeviceArray(out)
+
+
+def _f32_threshold(t) -> float:
+  """The double to compare a float32 quantity with so that the result is NumPy's
+  `float32_array > t`: a Python number or a float32 / float16 scalar is cast to
+  float32 first (NEP 50), a float64 (or int64) scalar compares in float64."""
+  if np.result_type(np.float32, t) == np.float32:
+    return float(np.float32(t))
+  return float(t)
+
+
+def reconcile_flows(flows, max_gradient: float, max_deviation: float,
+                    min_patch_size: int, min_delta_z: float = 0) -> DeviceArray:
+  """Reconciles multiple flows.
+
+  Same contract as the reference: `flows` is a sequence of [c, z, y, x] flows
+  (c = 2 or 3, all of one shape), or one [K, c, z, y, x] array, in order of
+  decreasing preference; later flows fill where the merged channel 0 is NaN
+  (for c = 3 only where |dz| >= `min_delta_z`), then vectors are invalidated where the gradient of channel
+  0 / 1 exceeds `max_gradient`, where channel 0 / 1 deviates from the 3 x 3
+  median by more than `max_deviation`, and where their 4-connected component
+  in the z slice has fewer than `min_patch_size` vectors (each test only when
+  its threshold is > 0).  Accepts NumPy arrays, torch tensors or DeviceArrays,
+  mixed; computes in float32 on the device without modifying the inputs and
+  returns a [c, z, y, x] DeviceArray.  The thresholds compare as in NumPy:
+  the gradient in float64 (np.diff's zero padding promotes the field), the
+  median deviation and |dz| in float32 against a Python number or float32
+  scalar and in float64 against a float64 scalar.
+  """
+  dev = _dev.device()
+  if isinstance(flows, (np.ndarray, torch.Tensor, DeviceArray)):
+    # one stacked array holds the K flows along its first axis
+    if len(flows.shape) != 5:
+      raise ValueError('a single array of flows must be [K, c, z, y, x]')
+    packed = _dev.as_device_f32(flows, dev, copy=False)
+    shape = tuple(packed.shape[1:])
+  else:
+    flows = list(flows)
+    if not flows:
+      raise ValueError('flows must hold at least one flow')
+    ts = [_dev.as_device_f32(f, dev, copy=False) for f in flows]
+    shape = tuple(ts[0].shape)
+    if any(tuple(t.shape) != shape for t in ts):
+      raise ValueError('all flows must have the same shape')
+    # [K, c, z, y, x]; one flow is passed as it is (never written)
+    packed = ts[0][None] if len(ts) == 1 else torch.stack(ts)
+  if len(shape) != 4 or shape[0] not in (2, 3) or min(shape) < 1 or packed.shape[0] < 1:
+    raise ValueError(f'flows must be [c, z, y, x] with c in (2, 3), got {shape}')
+  d = _abi.SfmReconcileDesc()
+  d.channels = shape[0]
+  d.shape = (C.c_int32 * 3)(*shape[1:])
+  d.num_flows = packed.shape[0]
+  # np.diff's zero padding makes the gradient float64 whatever the threshold
+  d.max_gradient = float(max_gradient) if max_gradient > 0 else 0.0
+  # a positive threshold that float32 rounds to 0 still enables the test: for a
+  # float32 x, `x > 0` is `x > 5e-324` in double
+  d.max_deviation = max(_f32_threshold(max_deviation), 5e-324) if max_deviation > 0 else 0.0
+  d.min_delta_z = _f32_threshold(min_delta_z)
+  # integer sizes: size < m <=> size < ceil(m)
+  d.min_patch_size = max(0, min(int(math.ceil(min_patch_size)), 2**62))
+  d.flows = packed.data_ptr()
+  lib = _abi.load()
+  nbytes = lib.sfm_reconcile_flows_workspace_bytes(C.byref(d))
+  ws = _dev.workspace(nbytes, dev)
+  d.workspace = ws.data_ptr()
+  d.workspace_bytes = ws.numel()
+  d.stream = _dev.stream_ptr()
+  out = torch.empty(shape, dtype=torch.float32, device=dev)
+  _abi.check(lib.sfm_reconcile_flows(C.byref(d), out.data_ptr()))
   return DeviceArray(out)
 
 
