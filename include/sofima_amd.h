@@ -359,6 +359,51 @@ size_t sfm_reconcile_flows_workspace_bytes(const SfmReconcileDesc* desc);
 int sfm_reconcile_flows(const SfmReconcileDesc* desc, float* out);
 
 /* ------------------------------------------------------------------------
+ * Inversion of an in-plane coordinate map, the step between mesh relaxation
+ * and warping.  Replaces the 2-D branch of map_utils.invert_map
+ * (map_utils.py:392-463): per z slice, the valid nodes (both channels finite)
+ * at their absolute positions rel + (j * stride_x + src_start_x * stride_x)
+ * (same for y) are triangulated (Delaunay) and the source coordinates
+ * trunc((j + src_start_x) * stride_x), trunc((i + src_start_y) * stride_y)
+ * are interpolated linearly at the queries (trunc(u * stride_x),
+ * trunc(v * stride_y)) of the output lattice; the result is made relative by
+ * subtracting (u * stride_x, v * stride_y).  Queries outside the convex hull,
+ * slices with fewer than 3 valid or only collinear nodes: NaN.  All arithmetic
+ * in double; combinatorial decisions use exact predicates.  The triangulation
+ * is verified on the device; status[z] is 0 for an answered slice, otherwise
+ * an OR of SFM_INVMAP_* reasons and the slice's output must not be used.
+ * At most 2^21 nodes per slice and 7936 nodes of the boundary set (valid
+ * nodes that are not interior vertices of the full-quad lattice part).
+ * ---------------------------------------------------------------------- */
+#define SFM_INVMAP_FOLD 1           /* a full quad is folded or degenerate     */
+#define SFM_INVMAP_NOT_DELAUNAY 2   /* an edge is not locally Delaunay         */
+#define SFM_INVMAP_BOUNDARY_CAP 4   /* more than 7936 boundary nodes           */
+#define SFM_INVMAP_CAPACITY 8       /* completion tables overflowed            */
+#define SFM_INVMAP_OVERLAP 16       /* an edge has two triangles on one side   */
+#define SFM_INVMAP_HULL 32          /* a border edge is not on the convex hull */
+#define SFM_INVMAP_COVER 64         /* the triangles do not tile the hull once */
+#define SFM_INVMAP_UNUSED 128       /* a valid node is not a vertex            */
+
+typedef struct SfmInvertMapDesc {
+  int32_t shape[3];             /* z, y, x of coord_map                      */
+  int32_t dst_shape[2];         /* y, x of the output lattice                */
+  int32_t src_start[2];         /* y, x: src_box.start - dst_box.start       */
+  double stride[2];             /* y, x, finite and > 0                      */
+  const double* coord_map;      /* device [2, z, y, x], relative format      */
+  int32_t* status;              /* device [z], caller-owned, written         */
+  void* workspace;              /* sfm_invert_map_workspace_bytes()          */
+  size_t workspace_bytes;
+  void* stream;
+} SfmInvertMapDesc;
+
+/* Host arithmetic only (callable without a GPU); 0 for a NULL descriptor or
+ * an empty shape. */
+size_t sfm_invert_map_workspace_bytes(const SfmInvertMapDesc* desc);
+/* out: device double [2, z, dst y, dst x]; must not overlap coord_map.
+ * Asynchronous: read status after the stream has finished. */
+int sfm_invert_map(const SfmInvertMapDesc* desc, double* out);
+
+/* ------------------------------------------------------------------------
  * Fold / stretch detection on a relaxed mesh, the step after relaxation.
  * Replaces map_utils.mask_irregular (map_utils.py:737-786): a node is bad when
  * the distance to its +x (+y) neighbour leaves [frac, max_frac] * stride; the

@@ -134,6 +134,20 @@ class SfmReconcileDesc(C.Structure):
   ]
 
 
+class SfmInvertMapDesc(C.Structure):
+  _fields_ = [
+      ('shape', i32 * 3),
+      ('dst_shape', i32 * 2),
+      ('src_start', i32 * 2),
+      ('stride', C.c_double * 2),
+      ('coord_map', C.c_void_p),
+      ('status', C.c_void_p),
+      ('workspace', C.c_void_p),
+      ('workspace_bytes', C.c_size_t),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmMaskIrregularDesc(C.Structure):
   _fields_ = [
       ('shape', i32 * 2),
@@ -381,6 +395,8 @@ SIGNATURES = {
     'sfm_clean_flow': (C.c_int, [C.POINTER(SfmCleanFlowDesc), C.c_void_p]),
     'sfm_reconcile_flows_workspace_bytes': (C.c_size_t, [C.POINTER(SfmReconcileDesc)]),
     'sfm_reconcile_flows': (C.c_int, [C.POINTER(SfmReconcileDesc), C.c_void_p]),
+    'sfm_invert_map_workspace_bytes': (C.c_size_t, [C.POINTER(SfmInvertMapDesc)]),
+    'sfm_invert_map': (C.c_int, [C.POINTER(SfmInvertMapDesc), C.c_void_p]),
     'sfm_mask_irregular': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,
                                      C.c_void_p]),
     'sfm_flow_starts': (C.c_int, [C.POINTER(SfmFlowStartsDesc)]),

@@ -25,6 +25,7 @@ SOURCES = {
                            os.environ.get('SFM_MFMA_FLAGS', '').split()),
     'sfm_maps.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MAPS_FLAGS', '').split(),
     'sfm_flowutils.hip': ['-ffp-contract=off'],
+    'sfm_invmap.hip': ['-ffp-contract=off'],
     'sfm_comm.hip': [],
     'sfm_warp.hip': ['-ffp-contract=off'],
 }

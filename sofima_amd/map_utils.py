@@ -1,9 +1,13 @@
-"""Coordinate-map composition on MI355X.
+"""Coordinate-map composition and inversion on MI355X.
 
-Drop-in for `map_utils.compose_maps_fast` of the reference
-(map_utils.py:616-734) and `map_utils.mask_irregular` (:737-786); the other
-functions of the reference's map_utils.py (Delaunay inversion, resampling, ...)
-are host geometry and out of scope.
+Drop-ins for `map_utils.compose_maps_fast` of the reference
+(map_utils.py:616-734), `map_utils.mask_irregular` (:737-786) and the 2-D
+branch of `map_utils.invert_map` (:392-463).  `invert_map` triangulates the
+deformed positions, so its Delaunay triangulation is unique and the device
+result has a parity contract.  `resample_map`, `compose_maps` and
+`fill_missing` triangulate the regular lattice, where every quad is
+co-circular and Qhull picks the diagonals arbitrarily; they stay host
+geometry and out of scope.
 """
 from __future__ import annotations
 
@@ -106,3 +110,95 @@ def mask_irregular(coord_map, stride: Sequence[float], frac: float,
     else:
       host[:, bad_h] = np.nan
   return bad_h
+
+
+# reasons of a refused slice (SFM_INVMAP_* in include/sofima_amd.h)
+_INVMAP_REASONS = (
+    (1, 'folded or degenerate quad'),
+    (2, 'edge not locally Delaunay'),
+    (4, 'more than 7936 boundary nodes'),
+    (8, 'completion tables overflowed'),
+    (16, 'overlapping triangles'),
+    (32, 'border edge off the convex hull'),
+    (64, 'triangles do not tile the convex hull'),
+    (128, 'valid node left out of the triangulation'),
+)
+
+
+def _box_xy(box, name):
+  start = [int(v) for v in np.asarray(box.start).ravel()]
+  size = [int(v) for v in np.asarray(box.size).ravel()]
+  if len(start) < 2 or len(size) < 2:
+    raise ValueError(f'{name} needs at least x and y in start and size')
+  return start, size
+
+
+def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
+  """Inverts a [2, z, y, x] coordinate map: (x, y) -> (u, v) becomes (u, v) -> (x, y).
+
+  Same contract as the 2-D branch of the reference: `coord_map` is in relative
+  format (NumPy, torch or DeviceArray, float32 or float64; never modified),
+  `src_box` / `dst_box` have `.start` / `.size` in xyz order (only x and y are
+  used), `stride` is a scalar or a (y, x) pair.  Per z slice the valid nodes
+  (both channels finite) are triangulated at their absolute positions
+  (Delaunay) and the source lattice coordinates are interpolated linearly at
+  the dst lattice; queries outside the convex hull and slices with fewer than
+  3 valid or only collinear nodes are NaN.  Computed in float64 on the device;
+  returns a float64 [2, z, dst y, dst x] DeviceArray in relative format.
+
+  The triangulation is verified on the device (one host sync reads the
+  per-slice status).  A slice that cannot be answered exactly -- folded, more
+  than 7936 boundary nodes, or a lattice part that is not Delaunay -- raises
+  SofimaAmdError naming the slice and the reason; it is never answered wrongly.
+  """
+  shape = tuple(int(v) for v in np.shape(coord_map)) if not isinstance(
+      coord_map, (torch.Tensor, DeviceArray)) else tuple(coord_map.shape)
+  if len(shape) != 4:
+    raise ValueError(f'coord_map must be [2, z, y, x], got shape {shape}')
+  dim = shape[0]
+  if dim == 3:
+    raise NotImplementedError(
+        'invert_map of 3-D maps (tetrahedra) is not on the device; it is a '
+        'follow-up of the 2-D inversion')
+  if dim != 2:
+    raise NotImplementedError(f'invert_map: {dim} channels')
+  sy, sx = (float(v) for v in _as_vec(stride, dim))
+  if not (np.isfinite(sx) and np.isfinite(sy) and sx > 0 and sy > 0):
+    raise ValueError(f'stride must be finite and positive, got {stride}')
+  src_start, src_size = _box_xy(src_box, 'src_box')
+  dst_start, dst_size = _box_xy(dst_box, 'dst_box')
+  if (shape[3], shape[2]) != (src_size[0], src_size[1]):
+    raise ValueError(f'box shape ({src_size}) mismatch with coord map ({shape})')
+  if min(shape[1:]) < 1 or dst_size[0] < 0 or dst_size[1] < 0:
+    raise ValueError(f'empty map or box: {shape}, {dst_size}')
+  dev = _dev.device()
+  if isinstance(coord_map, DeviceArray):
+    coord_map = coord_map.tensor
+  if isinstance(coord_map, torch.Tensor):
+    m = coord_map.to(device=dev, dtype=torch.float64).contiguous()
+  else:
+    m = _dev.upload(np.ascontiguousarray(np.asarray(coord_map, dtype=np.float64)), dev)
+  d = _abi.SfmInvertMapDesc()
+  d.shape = (C.c_int32 * 3)(*shape[1:])
+  d.dst_shape = (C.c_int32 * 2)(dst_size[1], dst_size[0])
+  d.src_start = (C.c_int32 * 2)(src_start[1] - dst_start[1], src_start[0] - dst_start[0])
+  d.stride = (C.c_double * 2)(sy, sx)
+  d.coord_map = m.data_ptr()
+  status = torch.empty(shape[1], dtype=torch.int32, device=dev)
+  d.status = status.data_ptr()
+  lib = _abi.load()
+  nbytes = lib.sfm_invert_map_workspace_bytes(C.byref(d))
+  ws = _dev.workspace(nbytes, dev)
+  d.workspace = ws.data_ptr()
+  d.workspace_bytes = ws.numel()
+  d.stream = _dev.stream_ptr()
+  out = torch.empty((2, shape[1], dst_size[1], dst_size[0]), dtype=torch.float64, device=dev)
+  _abi.check(lib.sfm_invert_map(C.byref(d), out.data_ptr()))
+  st = status.cpu().numpy()
+  bad = np.flatnonzero(st)
+  if bad.size:
+    z = int(bad[0])
+    why = ', '.join(r for bit, r in _INVMAP_REASONS if st[z] & bit)
+    more = f' ({bad.size} slices refused: {bad.tolist()[:8]})' if bad.size > 1 else ''
+    raise _abi.SofimaAmdError(f'invert_map: slice {z} refused: {why}{more}')
+  return DeviceArray(out)
