@@ -33,9 +33,11 @@
 extern "C" {
 #endif
 
-#define SFM_ABI_VERSION 8   /* 4: SfmProfile.mfma_issued; sfm_mesh_relax_banded; 5: SfmWarpDesc.coord_map_f64;
+#define SFM_ABI_VERSION 9   /* 4: SfmProfile.mfma_issued; sfm_mesh_relax_banded; 5: SfmWarpDesc.coord_map_f64;
                                 6: SfmBandedDesc.host_halo / host_allgather / host_user;
-                                7: sfm_ndimage_warp; 8: SfmProfile.tiles_abandoned */
+                                7: sfm_ndimage_warp; 8: SfmProfile.tiles_abandoned;
+                                9: SfmMaskIrregularDesc and SfmCleanFlowDesc carry
+                                   double thresholds */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -299,16 +301,18 @@ int sfm_compose_maps(const SfmComposeDesc* desc, float* out);
  * Replaces flow_utils.clean_flow (flow_utils.py:37-78): invalidates (NaN)
  * vectors with low peak sharpness / peak ratio, too large components, or a
  * too large deviation from the 3 x 3 (x 3) median of the nan_to_num'ed field
- * (scipy.ndimage.median_filter, mode "reflect").
+ * (scipy.ndimage.median_filter, mode "reflect").  The float32 quantities are
+ * compared with the thresholds in double: to compare in float32, as NumPy does
+ * with a Python number, pass the threshold rounded to float32.
  * ---------------------------------------------------------------------- */
 typedef struct SfmCleanFlowDesc {
   int32_t dim;                  /* 2 or 3 spatial dimensions                 */
   int32_t channels;             /* dim .. dim + 2 input channels             */
   int32_t shape[3];             /* z, y, x                                   */
-  float min_peak_ratio;
-  float min_peak_sharpness;
-  float max_magnitude;          /* <= 0: not applied                         */
-  float max_deviation;          /* <= 0: not applied                         */
+  double min_peak_ratio;
+  double min_peak_sharpness;
+  double max_magnitude;         /* <= 0: not applied                         */
+  double max_deviation;         /* <= 0: not applied                         */
   const float* flow;            /* device [channels, z, y, x]                */
   void* stream;
 } SfmCleanFlowDesc;
@@ -406,16 +410,19 @@ int sfm_invert_map(const SfmInvertMapDesc* desc, double* out);
 /* ------------------------------------------------------------------------
  * Fold / stretch detection on a relaxed mesh, the step after relaxation.
  * Replaces map_utils.mask_irregular (map_utils.py:737-786): a node is bad when
- * the distance to its +x (+y) neighbour leaves [frac, max_frac] * stride; the
- * bad set is dilated `dilation_iters` times with the full 3 x 3 structure and
- * the map is NaN'ed there in place.
+ * the distance to its +x (+y) neighbour leaves [min_dist, max_dist]; the bad
+ * set is dilated `dilation_iters` times with the full 3 x 3 structure and the
+ * map is NaN'ed there in place.  The neighbour difference is taken in float32
+ * (np.diff of a float32 map); the stride is added and the sum compared with
+ * the limits in double, as NumPy >= 2 does with a float64 stride scalar.  The
+ * caller forms the limits (frac * stride, max_frac * stride) in double.
  * ---------------------------------------------------------------------- */
 typedef struct SfmMaskIrregularDesc {
   int32_t shape[2];             /* y, x                                      */
-  float stride[2];              /* x, y (the reference's order)              */
-  float frac;
-  float max_frac;
   int32_t dilation_iters;
+  double stride[2];             /* x, y (the reference's order)              */
+  double min_dist[2];           /* x, y: frac * stride                       */
+  double max_dist[2];           /* x, y: max_frac * stride                   */
   void* stream;
 } SfmMaskIrregularDesc;
 

@@ -6,13 +6,17 @@ A NumPy / SciPy restatement of `warp.warp_subvolume` (/root/reference/warp.py:
 the reference makes (`cv2.convertMaps` to CV_16SC2, `cv2.remap` with a zero
 constant border).  Never imported by anything under `sofima_amd/`.
 
-PARITY UNPINNED beyond the reference's known-answer tests: OpenCV (cv2) cannot
-be installed in the build container, so neither this oracle nor the HIP path
-could be compared with the reference's output; the fixed-point semantics below
-follow OpenCV's published implementation (imgwarp.cpp: initInterTab2D,
-remapNearest / remapBilinear / remapLanczos4, 5 fractional map bits, 15-bit
-weights for 8-bit images).  Pinned by tests/warp_test.py:27-82 (re-typed in
-tests/test_reference_kats.py / tests/test_gpu_warp.py).
+OpenCV (cv2) is not available to the test suite, so neither this oracle nor the
+HIP path could be compared with the reference's output; the fixed-point
+semantics below follow OpenCV's published implementation (imgwarp.cpp:
+initInterTab2D, remapNearest / remapBilinear / remapLanczos4, 5 fractional map
+bits, 15-bit weights for 8-bit images).  PINNED: tests/warp_test.py:27-82
+(re-typed in tests/test_reference_kats.py / tests/test_gpu_warp.py), and tap
+geometry, kernels, zero border and coordinate quantisation against the
+independent float64 resampling reference of tests/test_gpu_postflow_edges.py
+(tests/test_postflow_refs.py: integer images within 1 count, 0.51 at 99.9 % of
+the pixels; float32 images within 4.1e-7 of the image maximum).  UNPINNED: bit
+parity with a real OpenCV build.
 """
 from __future__ import annotations
 

@@ -109,10 +109,10 @@ class SfmCleanFlowDesc(C.Structure):
       ('dim', i32),
       ('channels', i32),
       ('shape', i32 * 3),
-      ('min_peak_ratio', C.c_float),
-      ('min_peak_sharpness', C.c_float),
-      ('max_magnitude', C.c_float),
-      ('max_deviation', C.c_float),
+      ('min_peak_ratio', C.c_double),
+      ('min_peak_sharpness', C.c_double),
+      ('max_magnitude', C.c_double),
+      ('max_deviation', C.c_double),
       ('flow', C.c_void_p),
       ('stream', C.c_void_p),
   ]
@@ -151,10 +151,10 @@ class SfmInvertMapDesc(C.Structure):
 class SfmMaskIrregularDesc(C.Structure):
   _fields_ = [
       ('shape', i32 * 2),
-      ('stride', C.c_float * 2),
-      ('frac', C.c_float),
-      ('max_frac', C.c_float),
       ('dilation_iters', i32),
+      ('stride', C.c_double * 2),
+      ('min_dist', C.c_double * 2),
+      ('max_dist', C.c_double * 2),
       ('stream', C.c_void_p),
   ]
 

@@ -25,7 +25,7 @@ struct CleanArgs {
   float* out;
   int dim, channels;
   int Z, Y, X;
-  float min_ratio, min_sharp, max_mag, max_dev;
+  double min_ratio, min_sharp, max_mag, max_dev;  // compared in double, see SfmCleanFlowDesc
 };
 
 // np.nan_to_num for float32: NaN -> 0, +-inf -> +-FLT_MAX.
@@ -75,9 +75,9 @@ __global__ void __launch_bounds__(kBlock) clean_flow_kernel(CleanArgs a) {
   bool bad = false;
   if (a.channels == a.dim + 2) {
     // comparisons with NaN are false, as in NumPy
-    bad = fabsf(a.flow[a.dim * n_vec + i]) < a.min_sharp;
+    bad = static_cast<double>(fabsf(a.flow[a.dim * n_vec + i])) < a.min_sharp;
     const float pr = fabsf(a.flow[(a.dim + 1) * n_vec + i]);
-    bad = bad || (pr > 0.f && pr < a.min_ratio);
+    bad = bad || (pr > 0.f && static_cast<double>(pr) < a.min_ratio);
   }
   float v[3];
   bool any_nan = false;
@@ -87,18 +87,18 @@ __global__ void __launch_bounds__(kBlock) clean_flow_kernel(CleanArgs a) {
   }
   // np.max over the components propagates NaN, and NaN > t is false
   if (!any_nan) {
-    if (a.max_mag > 0.f) {
+    if (a.max_mag > 0.0) {
       float m = 0.f;
       for (int c = 0; c < a.dim; ++c) m = fmaxf(m, fabsf(v[c]));
-      bad = bad || m > a.max_mag;
+      bad = bad || static_cast<double>(m) > a.max_mag;
     }
-    if (a.max_dev > 0.f) {
+    if (a.max_dev > 0.0) {
       float m = 0.f;
       for (int c = 0; c < a.dim; ++c) {
         const float med = window_median(a.flow + c * n_vec, a, z, y, x);
         m = fmaxf(m, fabsf(med - v[c]));
       }
-      bad = bad || m > a.max_dev;
+      bad = bad || static_cast<double>(m) > a.max_dev;
     }
   }
   for (int c = 0; c < a.dim; ++c) a.out[c * n_vec + i] = bad ? NAN : v[c];
@@ -108,16 +108,18 @@ struct IrregArgs {
   float* map;          // [2, Y, X]
   unsigned char* bad;  // [Y, X]
   int Y, X, iters;
-  float sx, sy, lo_x, lo_y, hi_x, hi_y;
+  double sx, sy, lo_x, lo_y, hi_x, hi_y;
 };
 
 // bad before dilation (map_utils.py:768-775); out-of-range nodes are not bad.
 __device__ __forceinline__ bool irregular_at(const IrregArgs& a, int y, int x) {
   if (y < 0 || y >= a.Y || x < 0 || x >= a.X) return false;
   const long long n = (long long)a.Y * a.X, i = (long long)y * a.X + x;
-  // np.diff padded with 0 at the far edge, then + stride
-  const float dx = (x + 1 < a.X ? a.map[i + 1] - a.map[i] : 0.f) + a.sx;
-  const float dy = (y + 1 < a.Y ? a.map[n + i + a.X] - a.map[n + i] : 0.f) + a.sy;
+  // np.diff in float32, padded with 0 at the far edge; the float64 stride
+  // scalar promotes the sum, and the comparisons, to double (NumPy >= 2)
+  const double dx = static_cast<double>(x + 1 < a.X ? a.map[i + 1] - a.map[i] : 0.f) + a.sx;
+  const double dy =
+      static_cast<double>(y + 1 < a.Y ? a.map[n + i + a.X] - a.map[n + i] : 0.f) + a.sy;
   return dx < a.lo_x || dy < a.lo_y || dx > a.hi_x || dy > a.hi_y;
 }
 
@@ -163,10 +165,10 @@ extern "C" int sfm_mask_irregular(const SfmMaskIrregularDesc* d, float* coord_ma
   a.iters = d->dilation_iters;
   a.sx = d->stride[0];
   a.sy = d->stride[1];
-  a.lo_x = d->frac * a.sx;
-  a.lo_y = d->frac * a.sy;
-  a.hi_x = d->max_frac * a.sx;
-  a.hi_y = d->max_frac * a.sy;
+  a.lo_x = d->min_dist[0];
+  a.lo_y = d->min_dist[1];
+  a.hi_x = d->max_dist[0];
+  a.hi_y = d->max_dist[1];
   const long long n = (long long)a.Y * a.X;
   const unsigned grid = static_cast<unsigned>((n + kBlock - 1) / kBlock);
   hipStream_t st = static_cast<hipStream_t>(d->stream);

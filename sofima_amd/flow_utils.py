@@ -28,7 +28,9 @@ def clean_flow(flow, min_peak_ratio: float, min_peak_sharpness: float,
   [dim, z, y, x] vector field with NaN where the sharpness / ratio / magnitude
   / deviation-from-the-3x3(x3)-median criteria fail.  Accepts NumPy arrays,
   torch tensors or DeviceArrays; the result stays on the device (np.asarray()
-  copies it back) and is computed in float32.
+  copies it back) and is computed in float32.  The thresholds compare as in
+  NumPy: in float32 against a Python number or float32 scalar, in float64
+  against a float64 scalar (see `_f32_threshold`).
   """
   assert dim in (2, 3)
   dev = _dev.device()
@@ -40,10 +42,12 @@ def clean_flow(flow, min_peak_ratio: float, min_peak_sharpness: float,
   d.dim = dim
   d.channels = f.shape[0]
   d.shape = (C.c_int32 * 3)(*f.shape[1:])
-  d.min_peak_ratio = float(min_peak_ratio)
-  d.min_peak_sharpness = float(min_peak_sharpness)
-  d.max_magnitude = float(max_magnitude)
-  d.max_deviation = float(max_deviation)
+  d.min_peak_ratio = _f32_threshold(min_peak_ratio)
+  d.min_peak_sharpness = _f32_threshold(min_peak_sharpness)
+  # a positive threshold that float32 rounds to 0 still enables the test: for a
+  # float32 x, `x > 0` is `x > 5e-324` in double
+  d.max_magnitude = max(_f32_threshold(max_magnitude), 5e-324) if max_magnitude > 0 else 0.0
+  d.max_deviation = max(_f32_threshold(max_deviation), 5e-324) if max_deviation > 0 else 0.0
   d.flow = f.data_ptr()
   d.stream = _dev.stream_ptr()
   out = torch.empty((dim,) + tuple(f.shape[1:]), dtype=torch.float32, device=dev)

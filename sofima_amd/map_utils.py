@@ -81,7 +81,18 @@ def mask_irregular(coord_map, stride: Sequence[float], frac: float,
   Same contract as the reference (map_utils.py:737-786): masked entries are
   replaced with NaN IN PLACE (NumPy arrays are written back; torch tensors /
   DeviceArrays are modified on the device) and the bool mask [y, x] is
-  returned.  `stride` is (x, y).  Computed in float32.
+  returned.  `stride` is (x, y).
+
+  Arithmetic: the neighbour differences are taken in float32; the stride is
+  added and the sums are compared with `frac * stride` / `max_frac * stride`
+  in double, the limits being formed on the host as Python floats.  That is
+  what the reference computes for a float32 map under NumPy >= 2 (NEP 50: the
+  float64 stride scalar promotes the sum), and it is the high-precision
+  answer.  NumPy 1.x's value-based casting would have added the stride in
+  float32 instead.  `stride` is read as float64 whatever its dtype.  A
+  float64 map is still narrowed to float32 first: the result equals the
+  reference's when its values are float32-representable and their differences
+  exact in float32, and can differ from it by the narrowing otherwise.
   """
   shape = np.shape(coord_map)
   assert len(shape) == 3
@@ -94,10 +105,11 @@ def mask_irregular(coord_map, stride: Sequence[float], frac: float,
   m = _dev.as_device_f32(coord_map, dev, copy=host is not None)
   d = _abi.SfmMaskIrregularDesc()
   d.shape = (C.c_int32 * 2)(int(shape[1]), int(shape[2]))
-  d.stride = (C.c_float * 2)(stride_x, stride_y)
-  d.frac = float(frac)
-  d.max_frac = float(max_frac)
   d.dilation_iters = int(dilation_iters)
+  frac, max_frac = float(frac), float(max_frac)
+  d.stride = (C.c_double * 2)(stride_x, stride_y)
+  d.min_dist = (C.c_double * 2)(frac * stride_x, frac * stride_y)
+  d.max_dist = (C.c_double * 2)(max_frac * stride_x, max_frac * stride_y)
   d.stream = _dev.stream_ptr()
   bad = torch.empty(tuple(shape[1:]), dtype=torch.uint8, device=dev)
   _abi.check(_abi.load().sfm_mask_irregular(C.byref(d), m.data_ptr(), bad.data_ptr()))

@@ -7,11 +7,16 @@ nodes to the output pixels (scipy RegularGridInterpolator in the reference),
 conversion to OpenCV's 1/32-pixel fixed-point map format and the `cv2.remap`
 resampling are fused, so the two dense float maps per section never exist.
 
-Parity note: OpenCV is not installable in the build container, so the
-resampling semantics (convertMaps rounding, the 32 x 32-phase weight tables of
+Parity note: OpenCV is not available to the test suite, so the resampling
+semantics (convertMaps rounding, the 32 x 32-phase weight tables of
 initInterTab2D with 15-bit fixed point for 8-bit images, constant zero border)
-are restated from OpenCV's published algorithm and pinned by the reference's
-own tests (tests/warp_test.py:27-82) only: "parity unpinned" beyond those.
+are restated from OpenCV's published algorithm.  Pinned: the reference's own
+tests (tests/warp_test.py:27-82), and tap geometry, interpolation kernels,
+border handling and the 1/32-pixel coordinate quantisation against an
+independent float64 resampling reference written from the definitions
+(tests/test_gpu_postflow_edges.py: integer images within 1 count, float32
+images within 1.64e-6 of the image maximum).  Not pinned: bit parity with a
+real OpenCV build (which tap takes a table's rounding remainder).
 `ndimage_warp` (warp.py:189-335), the SciPy-only rendering path, is built as
 well and IS pinned: the reference function runs through the golden shim and
 the kernel reproduces its output bit for bit (tests/golden/ndimage_warp.npz).

@@ -1,6 +1,8 @@
 """warp.warp_subvolume on the HIP path (-m gpu): the reference's known-answer
-tests (tests/warp_test.py:27-82) and the oracle.  OpenCV is not installable
-here: parity beyond the KATs is unpinned (see oracle/warp_oracle.py)."""
+tests (tests/warp_test.py:27-82) and the oracle.  OpenCV is not available
+here: tap geometry, kernels, border and coordinate quantisation are pinned by
+the analytic float64 reference of tests/test_gpu_postflow_edges.py; bit parity
+with a real OpenCV build is not (see oracle/warp_oracle.py)."""
 import types
 
 import numpy as np
