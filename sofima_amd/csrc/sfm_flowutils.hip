@@ -183,8 +183,10 @@ extern "C" int sfm_mask_irregular(const SfmMaskIrregularDesc* d, float* coord_ma
 //   (maximum_filter(img, size) - minimum_filter(img, size)) < range_limit  [| extra]
 // scipy.ndimage filters, mode "reflect", origin 0: the window of pixel i covers
 // [i - size / 2, i - size / 2 + size - 1] per axis.  uint8 images subtract in
-// uint8 (max >= min: no wrap) and compare as integers against the limit;
-// float images subtract and compare in float32.
+// uint8 (max >= min: no wrap), float images in float32; the difference, exact
+// in double, is compared with the limit in double.  The host passes the
+// double that reproduces NumPy's comparison for the image dtype and the kind
+// of scalar it was given (stitch_rigid._range_limit).
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -216,8 +218,7 @@ range_mask_kernel(const T* __restrict__ img, const uint8_t* __restrict__ extra,
       mn = v < mn ? v : mn;
     }
   }
-  // NumPy compares the (uint8 | float32) difference with the Python scalar in
-  // double precision for floats' sake; both are exact in double.
+  // both sides are exact in double
   const T diff = static_cast<T>(mx - mn);
   uint8_t m = static_cast<double>(diff) < limit ? 1 : 0;
   if (extra) m |= extra[i] != 0;

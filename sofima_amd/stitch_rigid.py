@@ -33,15 +33,51 @@ MaskMap = Mapping[TileXY, np.ndarray]
 Vector = tuple[int, int] | tuple[int, int, int] | tuple[int] | tuple[Any, ...]
 
 
+def _given_dtype(img) -> np.dtype:
+  """dtype of an image as the caller passed it (before any narrowing); float32
+  for torch dtypes NumPy has no name for (bfloat16, ...), which are narrowed to
+  float32 anyway."""
+  if isinstance(img, _dev.DeviceArray):
+    img = img.tensor
+  if isinstance(img, torch.Tensor):
+    try:
+      return np.dtype(str(img.dtype).replace('torch.', ''))
+    except TypeError:
+      return np.dtype(np.float32)
+  return img.dtype
+
+
+def _range_limit(dtype: np.dtype, range_limit) -> float:
+  """The double to compare the window range of a `dtype` image with so that the
+  result is NumPy's `range < range_limit` (NEP 50, like
+  `flow_utils._f32_threshold`): the limit rounds to float32 only where NumPy
+  itself compares in float32 -- a float32 image against a Python number or a
+  float32 scalar, an integer image against a float32 scalar.  A float64 or
+  int64 scalar, and a Python float against an integer image, compare in
+  double; integer limits are exact either way."""
+  if np.result_type(dtype, range_limit) == np.float32:
+    return float(np.float32(range_limit))
+  return float(range_limit)
+
+
 def range_mask(img, range_limit: float, filter_size: int = 10,
                extra_mask=None) -> torch.Tensor:
   """Device mask of the pixels with too little local dynamic range
   (stitch_rigid.py:47-60), optionally OR-ed with `extra_mask`.
 
+  uint8 images stay uint8; uint16 and float32 images are processed as float32
+  (exact for uint16) and `range_limit` compares as in NumPy for the dtype the
+  image was given in (see `_range_limit`).  Images of any other dtype are
+  narrowed to float32 first: their window ranges are float32 roundings of what
+  the reference computes in the original dtype.
+
   Returns a uint8 CUDA tensor [y, x] (1 = masked) that `flow_field` accepts
   as `pre_mask` / `post_mask` without a host round trip.
   """
   dev = _dev.device()
+  if not isinstance(img, (_dev.DeviceArray, torch.Tensor)):
+    img = np.asarray(img)
+  given = _given_dtype(img)
   t, dtype = _dev.as_device_image(img, dev)
   if t.ndim != 2:
     raise ValueError('range masks are defined for 2-d images')
@@ -49,9 +85,7 @@ def range_mask(img, range_limit: float, filter_size: int = 10,
   d.dtype = dtype
   d.shape = (C.c_int32 * 2)(int(t.shape[0]), int(t.shape[1]))
   d.filter_size = int(filter_size)
-  # float images compare in float32 (NumPy's weak Python-scalar promotion)
-  d.range_limit = float(np.float32(range_limit)) if dtype == _abi.DTYPE_F32 \
-      else float(range_limit)
+  d.range_limit = _range_limit(given, range_limit)
   d.image = t.data_ptr()
   extra = _dev.as_device_mask(extra_mask, dev)
   if extra is not None:
