@@ -8,6 +8,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 
 #include "../../include/sofima_amd.h"
 
@@ -46,6 +47,23 @@ inline const char* measure_option(const char* name) {
 #endif
 }
 std::string option_str(const char* name);   // copy; empty when unset
+// Typed reads.  on: true unless the value starts with '0'.  tri: 0 / 1 for a value
+// that starts with '0' / '1', -1 when unset or anything else.  int: atoi when set.
+inline bool value_on(const char* e) { return !(e && e[0] == '0'); }
+inline int value_tri(const char* e) { return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1; }
+inline int value_int(const char* e, int dflt) { return e ? std::atoi(e) : dflt; }
+inline bool option_on(const char* name) { return value_on(option(name)); }
+inline int option_tri(const char* name) { return value_tri(option(name)); }
+inline int option_int(const char* name, int dflt) { return value_int(option(name), dflt); }
+inline bool measure_option_on(const char* name) { return value_on(measure_option(name)); }
+inline int measure_option_tri(const char* name) { return value_tri(measure_option(name)); }
+inline int measure_option_int(const char* name, int dflt) {
+  return value_int(measure_option(name), dflt);
+}
+
+// Compute units of the current device (hipGetDevice), looked up once per device;
+// 256 when the query fails.
+int device_cus();
 
 // FIRE scalars as the mesh kernels keep them on the device (sfm_mesh.hip) and
 // the pending per-step corrections derived from the previous step's sums.

@@ -53,6 +53,21 @@ std::string option_str(const char* name) {
   return v ? std::string(v) : std::string();
 }
 
+int device_cus() {
+  static std::mutex mu;
+  static std::map<int, int> cus_of;   // by device ordinal
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  std::lock_guard<std::mutex> lk(mu);
+  int& cus = cus_of[dev];
+  if (cus == 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+    if (cus <= 0) cus = 256;
+  }
+  return cus;
+}
+
 namespace {
 std::mutex g_prof_mu;
 std::atomic<bool> g_prof_on{false};

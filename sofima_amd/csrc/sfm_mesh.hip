@@ -3163,11 +3163,6 @@ int build_params(const SfmMeshDesc* d, MeshParams* p) {
   return SFM_OK;
 }
 
-bool small_enabled() {
-  const char* e = sfm::option("SFM_MESH_SMALL");  // "0": the launch-per-kernel path
-  return !(e && e[0] == '0');
-}
-
 // Plan of integrate_march3d_kernel for a mesh: the thread tile (halo included) that
 // wastes the fewest thread slots, and enough chunks of planes to fill the CUs.
 struct March3dPlan {
@@ -3177,28 +3172,14 @@ struct March3dPlan {
   size_t lds = 0;
 };
 
-int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 March3dPlan plan_march3d(const MeshParams& p) {
   March3dPlan best;
   // SFM_MESH_MARCH3D: "0" off, "1" on for every default-link volume, else by size
-  const char* e = sfm::option("SFM_MESH_MARCH3D");
-  if (e && e[0] == '0') return best;
+  const int mode = sfm::option_tri("SFM_MESH_MARCH3D");
+  if (mode == 0) return best;
   if (p.ncomp != 3 || !p.default_links || p.force_kind != SFM_FORCE_SPRINGS) return best;
-  const bool forced = e && e[0] == '1';
-  if (!forced && p.N < kMarch3dMinNodes) return best;
-  const char* te = sfm::option("SFM_MESH_MARCH3D_T");
-  const int t_only = te ? atoi(te) : 0;
+  if (mode != 1 && p.N < kMarch3dMinNodes) return best;
+  const int t_only = sfm::option_int("SFM_MESH_MARCH3D_T", 0);
   if ((unsigned long long)p.N * 12ull >= (1ull << 32)) return best;  // 32-bit byte offsets
   long long best_cost = 0;
   for (int T : {1024, 512, 256}) {
@@ -3233,13 +3214,13 @@ March3dPlan plan_march3d(const MeshParams& p) {
     best.T = 0;
     return best;
   }
-  const long long slots = std::min<long long>((long long)device_cus() * per_cu, kMaxBlocks);
+  const long long slots = std::min<long long>((long long)sfm::device_cus() * per_cu, kMaxBlocks);
   const long long planes = cols * p.Z;
   // every workgroup the same number of planes (a run that crosses into the next column
   // pays one more start-up plane); not below 8 planes per workgroup
   long long run = std::max<long long>((planes + slots - 1) / slots, std::min<long long>(8, p.Z));
-  const char* ze = sfm::option("SFM_MESH_MARCH3D_ZC");
-  if (ze && atoi(ze) > 0) run = atoi(ze);
+  const int zc = sfm::option_int("SFM_MESH_MARCH3D_ZC", 0);
+  if (zc > 0) run = zc;
   if ((planes + run - 1) / run > kMaxBlocks) run = (planes + kMaxBlocks - 1) / kMaxBlocks;
   best.g.cols = static_cast<int>(cols);
   best.g.run = static_cast<int>(run);
@@ -3251,13 +3232,10 @@ template <int T, bool PREFER>
 int launch_march3d_t(const March3dPlan& m, hipStream_t st, const float* x, float* v, float* a,
                      const float* prev, const MeshParams& p, const Scalars* scal, float cap,
                      float* partials) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    SFM_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&integrate_march3d_kernel<T, PREFER>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 36 * T * static_cast<int>(sizeof(float))));
-    attr_set = true;
-  }
+  // (a per-device attribute; set before every launch: a host-side call, nothing enqueued)
+  SFM_HIP_CHECK(hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&integrate_march3d_kernel<T, PREFER>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, 36 * T * static_cast<int>(sizeof(float))));
   hipLaunchKernelGGL((integrate_march3d_kernel<T, PREFER>), dim3(m.grid), dim3(T), m.lds, st, x,
                      v, a, prev, p, scal, cap, partials, m.g);
   SFM_LAUNCH_CHECK();
@@ -3276,11 +3254,6 @@ int launch_march3d(const March3dPlan& m, hipStream_t st, const float* x, float* 
     default: SFM_MARCH(256);
   }
 #undef SFM_MARCH
-}
-
-bool persistent_enabled() {
-  const char* e = sfm::option("SFM_MESH_PERSISTENT");
-  return !(e && e[0] == '0');
 }
 
 int grid_for(long long n) {
@@ -3319,27 +3292,12 @@ struct TilePlan {
   long long packed_tiles = 0;   // workgroups of a packed launch (== tiles without packing)
 };
 
-bool pack_enabled() {
-  const char* e = sfm::option("SFM_MESH_PACK");   // "0": every tile row of the last column its own workgroup
-  return !(e && e[0] == '0');
-}
-
-bool fuse_target_enabled() {
-  const char* e = sfm::option("SFM_MESH_FUSE_TARGET");  // "0": advance + target + integrate
-  return !(e && e[0] == '0');
-}
-
-bool tiled_enabled() {
-  const char* e = sfm::option("SFM_MESH_TILED");
-  return !(e && e[0] == '0');
-}
-
 TilePlan plan_tiles(int ncomp, long long planes, int Y, int X) {
   TilePlan best;
   // every spring once (integrate_shared2d_kernel): 16 x 62 tiles, a lane per
   // column; pays off unless most of a 64-lane row would hang over the mesh
   // (narrower meshes take the advance / integrate pair)
-  if (ncomp != 2 || !tiled_enabled() || X < 40 || Y < 4) return best;
+  if (ncomp != 2 || !sfm::option_on("SFM_MESH_TILED") || X < 40 || Y < 4) return best;
   best.ty = kSY;
   best.tx = kSX;
   best.nty = (Y + kSY - 1) / kSY;
@@ -3395,53 +3353,153 @@ MeshWorkspace carve(void* ws, size_t prev_floats, size_t alt_floats, long long t
   return w;
 }
 
-MeshWorkspace carve_for(const SfmMeshDesc* d, void* ws, TilePlan* plan) {
-  const size_t n = (size_t)d->shape[0] * d->shape[1] * d->shape[2] * d->shape[3];
-  TilePlan t = d->force_kind == SFM_FORCE_SPRINGS
-                   ? plan_tiles(d->ncomp, (long long)d->shape[0] * d->shape[1],
-                                d->shape[2], d->shape[3])
-                   : TilePlan();
-  if (plan) *plan = t;
-  const size_t cn = (size_t)d->ncomp * n;
+// XCD-contiguous tile order: on once there are several rounds of workgroups
+// (measured after the SGPR spills were gone: [2,4,2048^2] 270 -> 261 us,
+// [2,64,204^2] 62.2 -> 58.6; [2,1,1000^2], one round of 1071 tiles: 31.1 -> 31.5).
+// tri = SFM_MESH_XCD: 0 off, 1 on for any grid of at least 64 tiles.
+int xcd_order(int tri, int grid) {
+  return tri == 0 ? 0 : grid >= (tri == 1 ? 64 : 2048) ? 1 : 0;
+}
+
+// Everything a chunk decides before its first launch: which integrator runs, its
+// grids, and the workspace both need.  sfm_mesh_workspace_bytes and the relax
+// calls carve from the same plan.
+struct ChunkPlan {
+  // workspace (from the desc alone: a sizing call's desc need not be complete)
+  TilePlan tiles;
+  size_t prev_floats = 0, alt_floats = 0, list_ints = 0;
+  int ncols = 0;
+  // integrator (only with MeshParams)
+  int grid = 0;              // per-node kernels
+  bool dyn_prev = false;     // prev = prev_fn(x) in front of every force evaluation
+  int persist_tile = 0;      // persistent single launch: 16 or 32 (0: not taken)
+  bool persist_spec = false;
+  bool small = false;        // one workgroup's worth of nodes: mesh_small_kernel
+  bool tiled = false, fuse_target = false, fused = false, pack = false;
+  int tgrid = 0, xcd_map = 0;
+  March3dPlan march;         // default-link volumes: every spring once
+  int part_rows = 0;         // rows of partial sums the step kernels leave
+  int finish_mode = 0;
+};
+
+// Makes no HIP call other than sfm::device_cus().
+ChunkPlan plan_chunk(const SfmMeshDesc* d, const MeshParams* pp) {
+  ChunkPlan c;
+  const size_t cn = (size_t)d->ncomp * d->shape[0] * d->shape[1] * d->shape[2] * d->shape[3];
+  if (d->force_kind == SFM_FORCE_SPRINGS)
+    c.tiles = plan_tiles(d->ncomp, (long long)d->shape[0] * d->shape[1], d->shape[2], d->shape[3]);
+  c.prev_floats = d->target ? cn : 0;
   // second (x, v, a) set: ping-pong of the fused tiled step, staging of the
   // persistent kernel's result
-  return carve(ws, d->target ? cn : 0,
-               (d->ncomp == 2 && !d->prev_cb && d->force_kind == SFM_FORCE_SPRINGS) ? cn : 0,
-               t.tiles,
-               d->shape[3], d->target ? sfm::target_list_ints(d->target) : 0);
+  c.alt_floats = (d->ncomp == 2 && !d->prev_cb && d->force_kind == SFM_FORCE_SPRINGS) ? cn : 0;
+  c.list_ints = d->target ? sfm::target_list_ints(d->target) : 0;
+  c.ncols = d->shape[3];
+  if (!pp) return c;
+
+  const MeshParams& p = *pp;
+  c.grid = grid_for(p.N);
+  c.dyn_prev = d->target || d->prev_cb;
+  // Persistent single-launch path for in-plane meshes that fit the chip.  Small
+  // tiles spread the (latency bound) step over more CUs; fall back to 32 x 32
+  // tiles when there would be more workgroups than CUs.
+  if (sfm::option_on("SFM_MESH_PERSISTENT") && p.ncomp == 2 && d->num_iters >= 1 &&
+      !c.dyn_prev && p.force_kind == SFM_FORCE_SPRINGS) {
+    const int only = sfm::option_int("SFM_MESH_TILE", -1);  // experiment: 16 or 32
+    const int cus = sfm::device_cus();
+    for (int t : {16, 32}) {
+      if (only != -1 && only != t) continue;
+      const long long nw = (long long)p.B * ((p.Y + t - 1) / t) * ((p.X + t - 1) / t);
+      if (nw <= kMaxWg && nw <= cus) {
+        c.persist_tile = t;
+        break;
+      }
+    }
+    c.persist_spec = p.fire && !p.remove_drift && sfm::option_on("SFM_MESH_SPECULATE");
+  }
+  // SFM_MESH_SMALL=0: the launch-per-kernel path
+  c.small = sfm::option_on("SFM_MESH_SMALL") && c.grid == 1 && d->num_iters > 0 && !c.dyn_prev &&
+            p.force_kind != SFM_FORCE_EXTERNAL && !p.drift_cols && p.own_y0 <= 0 &&
+            p.own_y1 >= p.Y;
+  c.tiled = c.tiles.tx && d->num_iters > 0;
+  // Native prev_fn on a tiled in-plane mesh: the target mesh is sampled from the
+  // positions AFTER the position update, which the target kernel forms itself
+  // from (x, v, a) on the overlap strips (sfm::AdvanceView) -- so the step is
+  // target mesh (strips only) + the fused integrator instead of advance + target
+  // mesh (all nodes) + integrate.  Same float operations: bit-identical.
+  // (SFM_MESH_FUSE_TARGET=0: advance + target + integrate)
+  c.fuse_target = c.tiled && d->target && c.alt_floats && sfm::option_on("SFM_MESH_FUSE_TARGET");
+  c.fused = c.tiled && (!c.dyn_prev || c.fuse_target);
+  // SFM_MESH_PACK=0: every tile row of the last column its own workgroup
+  c.pack = c.tiles.pack_S >= 2 && sfm::option_on("SFM_MESH_PACK");
+  c.tgrid = static_cast<int>(c.pack ? c.tiles.packed_tiles : c.tiles.tiles);
+  c.xcd_map = xcd_order(sfm::option_tri("SFM_MESH_XCD"), c.tgrid);
+  if (!c.tiled && !c.small) c.march = plan_march3d(p);
+  c.part_rows = c.march.T ? c.march.grid : c.grid;
+  c.finish_mode = c.tiled ? 2 : d->num_iters > 0 ? 1 : 0;
+  return c;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t sfm_mesh_workspace_bytes(const SfmMeshDesc* d) {
-  if (!d) return 0;
-  return carve_for(d, nullptr, nullptr).bytes;
+MeshWorkspace carve_for(const ChunkPlan& c, void* ws) {
+  return carve(ws, c.prev_floats, c.alt_floats, c.tiles.tiles, c.ncols, c.list_ints);
 }
 
-int sfm_mesh_force(const SfmMeshDesc* d, float* out) {
-  MeshParams p;
-  if (int rc = build_params(d, &p)) return rc;
-  if (!d->x || !out) return sfm::fail(SFM_ERR_INVALID, "x/out is NULL");
-  if (p.force_kind == SFM_FORCE_EXTERNAL)
-    return sfm::fail(SFM_ERR_INVALID, "sfm_mesh_force: the external force is the caller's");
-  hipStream_t st = static_cast<hipStream_t>(d->stream);
-  const int grid = grid_for(p.N);
-  if (p.ncomp == 2)
-    hipLaunchKernelGGL(force_kernel<2>, dim3(grid), dim3(kBlock), 0, st, d->x,
-                       nullptr, out, p, 0.f, 0);
-  else
-    hipLaunchKernelGGL(force_kernel<3>, dim3(grid), dim3(kBlock), 0, st, d->x,
-                       nullptr, out, p, 0.f, 0);
-  SFM_LAUNCH_CHECK();
+// The KERNEL<2> or KERNEL<3> instance for a mesh of NCOMP components.
+#define SFM_LAUNCH_NCOMP(KERNEL, NCOMP, GRID, BLOCK, STREAM, ...)                         \
+  do {                                                                                    \
+    if ((NCOMP) == 2)                                                                     \
+      hipLaunchKernelGGL(KERNEL<2>, dim3(GRID), dim3(BLOCK), 0, STREAM, __VA_ARGS__);     \
+    else                                                                                  \
+      hipLaunchKernelGGL(KERNEL<3>, dim3(GRID), dim3(BLOCK), 0, STREAM, __VA_ARGS__);     \
+    SFM_LAUNCH_CHECK();                                                                   \
+  } while (0)
+
+// FIRE scalars a chunk starts from.
+Scalars initial_scalars(const SfmFireState& fire) {
+  Scalars s0;
+  std::memset(&s0, 0, sizeof(s0));
+  s0.dt = fire.dt;
+  s0.alpha = fire.alpha;
+  s0.n_pos = 0;  // restarts every call (mesh.py:513)
+  s0.cap = fire.cap;
+  s0.gate = 1.f;
+  return s0;
+}
+
+// End of a chunk: the final scalars and `n_stats` floats of statistics (and the
+// persistent kernel's abort flag) come to the host; waits for the stream.
+int fetch_results(hipStream_t st, const Scalars* scal, Scalars* s1, const float* stats, float* hs,
+                  size_t n_stats, const int* abort_flag = nullptr, int* aborted = nullptr) {
+  SFM_HIP_CHECK(hipMemcpyAsync(s1, scal, sizeof(*s1), hipMemcpyDeviceToHost, st));
+  SFM_HIP_CHECK(hipMemcpyAsync(hs, stats, sizeof(float) * n_stats, hipMemcpyDeviceToHost, st));
+  if (abort_flag)
+    SFM_HIP_CHECK(hipMemcpyAsync(aborted, abort_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  SFM_HIP_CHECK(hipStreamSynchronize(st));
   return SFM_OK;
 }
 
-int sfm_mesh_relax_chunk(const SfmMeshDesc* d, SfmFireState* fire,
-                         SfmChunkStats* stats) {
-  MeshParams p;
-  if (int rc = build_params(d, &p)) return rc;
+void carry_fire(const Scalars& s1, SfmFireState* fire) {
+  fire->dt = s1.dt;
+  fire->alpha = s1.alpha;
+  fire->n_pos = s1.n_pos;
+  fire->cap = s1.cap;
+}
+
+// stats = {e_kin, v_max} on the device.  With an abort flag that turns out set,
+// `fire` and `out` stay as they are.
+int read_back(hipStream_t st, const Scalars* scal, const float* stats, bool fire_on,
+              SfmFireState* fire, SfmChunkStats* out, const int* abort_flag = nullptr,
+              int* aborted = nullptr) {
+  Scalars s1;
+  float hs[2];
+  if (int rc = fetch_results(st, scal, &s1, stats, hs, 2, abort_flag, aborted)) return rc;
+  if (aborted && *aborted) return SFM_OK;
+  if (fire_on) carry_fire(s1, fire);
+  out->e_kin = hs[0];
+  out->v_max = hs[1];
+  return SFM_OK;
+}
+
+int validate_chunk(const SfmMeshDesc* d, const SfmFireState* fire, const SfmChunkStats* stats) {
   if (!d->x || !d->v || !d->a)
     return sfm::fail(SFM_ERR_INVALID, "x/v/a must be device pointers");
   if (!fire || !stats) return sfm::fail(SFM_ERR_INVALID, "fire/stats is NULL");
@@ -3457,316 +3515,260 @@ int sfm_mesh_relax_chunk(const SfmMeshDesc* d, SfmFireState* fire,
     return sfm::fail(SFM_ERR_INVALID, "prev_fn: either the native target mesh or a callback");
   if (d->prev_cb && !d->ext_prev)
     return sfm::fail(SFM_ERR_INVALID, "prev_cb needs the ext_prev buffer");
-  TilePlan tiles;
-  MeshWorkspace w = carve_for(d, d->workspace, &tiles);
-  if (!d->workspace || d->workspace_bytes < w.bytes)
-    return sfm::fail(SFM_ERR_WORKSPACE, "mesh workspace needs %zu bytes, got %zu",
-                     w.bytes, d->workspace_bytes);
-  hipStream_t st = static_cast<hipStream_t>(d->stream);
-  const int grid = grid_for(p.N);
-  const float* prev_ptr = d->target ? w.prev_buf : d->prev_cb ? d->ext_prev : d->prev;
+  return SFM_OK;
+}
+
+// One chunk on one stream: the multi-launch integrators and, in front of them,
+// the persistent single launch.
+struct ChunkRun {
+  const SfmMeshDesc* d;
+  const MeshParams& p;
+  const ChunkPlan& c;
+  const MeshWorkspace& w;
+  hipStream_t st;
+  Scalars s0;
+  float cap0;
+  const float* prev_ptr;
+  int cur = 0;   // scal[cur]: the scalars the next kernel reads
+  int in = 0;    // fused tiled step: the (x, v, a) set the next step reads
+  // column means of the state in (xs, vs): ~16 rows per thread and chunk
+  int col_chunks = 0, col_rows_per = 0;
+
+  ChunkRun(const SfmMeshDesc* d_, const MeshParams& p_, const ChunkPlan& c_,
+           const MeshWorkspace& w_, const SfmFireState& fire)
+      : d(d_), p(p_), c(c_), w(w_), st(static_cast<hipStream_t>(d_->stream)),
+        s0(initial_scalars(fire)), cap0(fire.cap),
+        prev_ptr(d_->target ? w_.prev_buf : d_->prev_cb ? d_->ext_prev : d_->prev) {
+    const long long col_rows = p.N / p.X;
+    const int col_groups = p.X <= kBlock ? kBlock / p.X : 1;
+    col_chunks = static_cast<int>(std::max<long long>(
+        1, std::min<long long>(kColChunksMax, (col_rows + col_groups * 16LL - 1) / (col_groups * 16LL))));
+    col_rows_per = static_cast<int>((col_rows + col_chunks - 1) / col_chunks);
+  }
+
+  int write_scalars() {
+    SFM_HIP_CHECK(hipMemcpyAsync(&w.scal[0], &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+    return SFM_OK;
+  }
+
   // prev = prev_fn(x) (mesh.py:429-430): the native target mesh, or the caller's
   // callable through prev_cb, re-evaluated in front of every force evaluation
-  const bool dyn_prev = d->target || d->prev_cb;
-  auto eval_prev = [&](hipStream_t s_) -> int {
-    if (d->target) return sfm::launch_target_mesh(d->target, d->x, w.prev_buf, s_);
+  int eval_prev() {
+    if (d->target) return sfm::launch_target_mesh(d->target, d->x, w.prev_buf, st);
     if (d->prev_cb && d->prev_cb(d->prev_user) != 0)
       return sfm::fail(SFM_ERR_INVALID, "mesh: the prev_fn callback failed");
     return SFM_OK;
-  };
-
-  Scalars s0;
-  std::memset(&s0, 0, sizeof(s0));
-  s0.dt = fire->dt;
-  s0.alpha = fire->alpha;
-  s0.n_pos = 0;  // restarts every call (mesh.py:513)
-  s0.cap = fire->cap;
-  s0.gate = 1.f;
-  SFM_HIP_CHECK(hipMemcpyAsync(&w.scal[0], &s0, sizeof(s0),
-                               hipMemcpyHostToDevice, st));
-
-  const float cap0 = fire->cap;
-
-  // Persistent single-launch path for in-plane meshes that fit the chip.
-  if (persistent_enabled() && p.ncomp == 2 && d->num_iters >= 1 && !dyn_prev &&
-      p.force_kind == SFM_FORCE_SPRINGS) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, dev) == hipSuccess)
-        cus = prop.multiProcessorCount;
-    }
-    // Small tiles spread the (latency bound) step over more CUs; fall back to
-    // 32 x 32 tiles when there would be more workgroups than CUs.
-    int tile = 0;
-    const char* force_tile = sfm::option("SFM_MESH_TILE");  // experiment: 16 or 32
-    for (int t : {16, 32}) {
-      if (force_tile && atoi(force_tile) != t) continue;
-      const long long nw = (long long)p.B * ((p.Y + t - 1) / t) * ((p.X + t - 1) / t);
-      if (nw <= kMaxWg && nw <= cus) {
-        tile = t;
-        break;
-      }
-    }
-    if (tile) {
-      const int nty = (p.Y + tile - 1) / tile, ntx = (p.X + tile - 1) / tile;
-      const long long n_wg = (long long)p.B * nty * ntx;
-      PersistArgs q;
-      q.comm = w.comm;
-      q.part = w.comm + (size_t)kMaxWg * 2 * Tile<32>::kSlot + 8;
-      q.abort = w.abort;
-      q.scal_in = &w.scal[0];
-      q.scal_out = &w.scal[1];
-      q.stat_partials = w.stat_part;
-      q.num_iters = d->num_iters;
-      q.cap0 = cap0;
-      q.nty = nty;
-      q.ntx = ntx;
-      q.n_wg = static_cast<int>(n_wg);
-      SFM_HIP_CHECK(hipMemsetAsync(w.comm, 0, w.comm_bytes, st));
-      sfm::prof_begin(sfm::kProfMesh, st);
-      const char* spec_env = sfm::option("SFM_MESH_SPECULATE");
-      const bool spec = p.fire && !p.remove_drift && !(spec_env && spec_env[0] == '0');
-      if (spec && tile == 16)
-        hipLaunchKernelGGL(mesh_persist2d_spec_kernel<16>, dim3(q.n_wg), dim3(spec_threads<16>()), 0, st,
-                           p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
-      else if (spec)
-        hipLaunchKernelGGL(mesh_persist2d_spec_kernel<32>, dim3(q.n_wg), dim3(1024), 0, st,
-                           p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
-      else if (tile == 16)
-        hipLaunchKernelGGL(mesh_persist2d_kernel<16>, dim3(q.n_wg), dim3(256), 0, st,
-                           p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
-      else
-        hipLaunchKernelGGL(mesh_persist2d_kernel<32>, dim3(q.n_wg), dim3(1024), 0, st,
-                           p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
-      sfm::prof_end(sfm::kProfMesh, st);
-      SFM_LAUNCH_CHECK();
-      hipLaunchKernelGGL(persist_commit_kernel, dim3(grid_for((long long)p.ncomp * p.N)),
-                         dim3(kBlock), 0, st, w.abort, w.alt[0], w.alt[1], w.alt[2], d->x,
-                         d->v, d->a, (long long)p.ncomp * p.N);
-      SFM_LAUNCH_CHECK();
-      hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, w.stat_part,
-                         q.n_wg, w.stats);
-      SFM_LAUNCH_CHECK();
-      Scalars s1;
-      float hs[2];
-      int aborted = 0;
-      SFM_HIP_CHECK(hipMemcpyAsync(&s1, &w.scal[1], sizeof(s1),
-                                   hipMemcpyDeviceToHost, st));
-      SFM_HIP_CHECK(hipMemcpyAsync(hs, w.stats, sizeof(hs), hipMemcpyDeviceToHost, st));
-      SFM_HIP_CHECK(hipMemcpyAsync(&aborted, w.abort, sizeof(int),
-                                   hipMemcpyDeviceToHost, st));
-      SFM_HIP_CHECK(hipStreamSynchronize(st));
-      if (!aborted) {
-        if (p.fire) {
-          fire->dt = s1.dt;
-          fire->alpha = s1.alpha;
-          fire->n_pos = s1.n_pos;
-          fire->cap = s1.cap;
-        }
-        stats->e_kin = hs[0];
-        stats->v_max = hs[1];
-        return SFM_OK;
-      }
-      // Timed out (workgroups not co-resident?): the commit kernel saw the
-      // abort flag and left x, v, a untouched; fall through to the
-      // multi-launch path.
-      SFM_HIP_CHECK(hipMemcpyAsync(&w.scal[0], &s0, sizeof(s0),
-                                   hipMemcpyHostToDevice, st));
-    }
   }
-#define SFM_MESH_DISPATCH(KERNEL, ...)                                       \
-  do {                                                                       \
-    if (p.ncomp == 2)                                                        \
-      hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(kBlock), 0, st,         \
-                         __VA_ARGS__);                                       \
-    else                                                                     \
-      hipLaunchKernelGGL(KERNEL<3>, dim3(grid), dim3(kBlock), 0, st,         \
-                         __VA_ARGS__);                                       \
-    SFM_LAUNCH_CHECK();                                                      \
-  } while (0)
 
   // The caller's mesh_force (SFM_FORCE_EXTERNAL) is evaluated on the host's
   // initiative right before the kernel that consumes it.
-  auto external_force = [&]() -> int {
+  int external_force() {
     if (p.force_kind != SFM_FORCE_EXTERNAL) return SFM_OK;
     if (d->force_cb(d->force_user) != 0)
       return sfm::fail(SFM_ERR_INVALID, "mesh: the external force callback failed");
     return SFM_OK;
-  };
+  }
 
-  // a = F(x) + pull(prev, cap)   (mesh.py:501); prev = prev_fn(x) if native
-  if (int rc = eval_prev(st)) return rc;
-  if (int rc = external_force()) return rc;
-  SFM_MESH_DISPATCH(force_kernel, d->x, prev_ptr, d->a, p, cap0, p.has_prev);
-
-  int cur = 0;
-  int finish_mode = d->num_iters > 0 ? 1 : 0;
-  // One workgroup's worth of nodes: every step in one launch (mesh_small_kernel).
-  const bool small = small_enabled() && grid == 1 && d->num_iters > 0 && !dyn_prev &&
-                     p.force_kind != SFM_FORCE_EXTERNAL && !p.drift_cols &&
-                     p.own_y0 <= 0 && p.own_y1 >= p.Y;
-  if (small) {
+  // Every step in one launch, the result handed over all or nothing.  *done: the
+  // chunk is finished.  Otherwise the kernel timed out (workgroups not
+  // co-resident?): the commit kernel saw the abort flag and left x, v, a
+  // untouched, the start scalars are uploaded again and the multi-launch path
+  // takes over.
+  int persistent(SfmFireState* fire, SfmChunkStats* stats, bool* done) {
+    const int tile = c.persist_tile;
+    const int nty = (p.Y + tile - 1) / tile, ntx = (p.X + tile - 1) / tile;
+    PersistArgs q;
+    q.comm = w.comm;
+    q.part = w.comm + (size_t)kMaxWg * 2 * Tile<32>::kSlot + 8;
+    q.abort = w.abort;
+    q.scal_in = &w.scal[0];
+    q.scal_out = &w.scal[1];
+    q.stat_partials = w.stat_part;
+    q.num_iters = d->num_iters;
+    q.cap0 = cap0;
+    q.nty = nty;
+    q.ntx = ntx;
+    q.n_wg = static_cast<int>((long long)p.B * nty * ntx);
+    SFM_HIP_CHECK(hipMemsetAsync(w.comm, 0, w.comm_bytes, st));
     sfm::prof_begin(sfm::kProfMesh, st);
-    if (p.ncomp == 2)
-      hipLaunchKernelGGL(mesh_small_kernel<2>, dim3(1), dim3(kBlock), 0, st, d->x, d->v, d->a,
-                         prev_ptr, p, w.scal, cap0, w.partials, d->num_iters);
+    if (c.persist_spec && tile == 16)
+      hipLaunchKernelGGL(mesh_persist2d_spec_kernel<16>, dim3(q.n_wg), dim3(spec_threads<16>()), 0, st,
+                         p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
+    else if (c.persist_spec)
+      hipLaunchKernelGGL(mesh_persist2d_spec_kernel<32>, dim3(q.n_wg), dim3(1024), 0, st,
+                         p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
+    else if (tile == 16)
+      hipLaunchKernelGGL(mesh_persist2d_kernel<16>, dim3(q.n_wg), dim3(256), 0, st,
+                         p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
     else
-      hipLaunchKernelGGL(mesh_small_kernel<3>, dim3(1), dim3(kBlock), 0, st, d->x, d->v, d->a,
-                         prev_ptr, p, w.scal, cap0, w.partials, d->num_iters);
+      hipLaunchKernelGGL(mesh_persist2d_kernel<32>, dim3(q.n_wg), dim3(1024), 0, st,
+                         p, d->x, d->v, w.alt[0], w.alt[1], w.alt[2], d->prev, q);
     sfm::prof_end(sfm::kProfMesh, st);
     SFM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(persist_commit_kernel, dim3(grid_for((long long)p.ncomp * p.N)),
+                       dim3(kBlock), 0, st, w.abort, w.alt[0], w.alt[1], w.alt[2], d->x,
+                       d->v, d->a, (long long)p.ncomp * p.N);
+    SFM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, w.stat_part, q.n_wg, w.stats);
+    SFM_LAUNCH_CHECK();
+    int aborted = 0;
+    if (int rc = read_back(st, &w.scal[1], w.stats, p.fire, fire, stats, w.abort, &aborted))
+      return rc;
+    *done = !aborted;
+    return aborted ? write_scalars() : SFM_OK;
   }
-  const bool tiled = tiles.tx && d->num_iters > 0;
-  float* bufs[2][3] = {{d->x, d->v, d->a}, {w.alt[0], w.alt[1], w.alt[2]}};
-  int in = 0;
-  // Native prev_fn on a tiled in-plane mesh: the target mesh is sampled from the
-  // positions AFTER the position update, which the target kernel forms itself
-  // from (x, v, a) on the overlap strips (sfm::AdvanceView) -- so the step is
-  // target mesh (strips only) + the fused integrator instead of advance + target
-  // mesh (all nodes) + integrate.  Same float operations: bit-identical.
-  const bool fuse_target = tiled && d->target && w.alt[0] && fuse_target_enabled();
-  const bool fused = tiled && (!dyn_prev || fuse_target);
-  if (fuse_target && w.target_list)
-    if (int rc = sfm::build_target_list(d->target, w.target_list, st)) return rc;
-  const bool pack = tiles.pack_S >= 2 && pack_enabled();
-  const int tgrid = static_cast<int>(pack ? tiles.packed_tiles : tiles.tiles);
-  // XCD-contiguous tile order: on once there are several rounds of workgroups
-  // (measured after the SGPR spills were gone: [2,4,2048^2] 270 -> 261 us,
-  // [2,64,204^2] 62.2 -> 58.6; [2,1,1000^2], one round of 1071 tiles: 31.1 -> 31.5).
-  // SFM_MESH_XCD=0 / 1: off / on for any grid of at least 64 tiles.
-  const char* xcd_opt = sfm::option("SFM_MESH_XCD");
-  const int xcd_map = xcd_opt && xcd_opt[0] == '0'   ? 0
-                      : xcd_opt && xcd_opt[0] == '1' ? (tgrid >= 64 ? 1 : 0)
-                                                     : (tgrid >= 2048 ? 1 : 0);
-  if (tiled) {
-    // LDS-tiled integrator (2-D): one launch per step, or advance + prev_fn +
-    // integrate when the spring targets depend on the advanced positions.
-    SFM_HIP_CHECK(hipMemsetAsync(w.ticket, 0, 2 * sizeof(int), st));
-    SFM_HIP_CHECK(hipMemsetAsync(w.tile_part, 0, (size_t)tiles.tiles * kNP * sizeof(u64), st));
-    finish_mode = 2;
+
+  // a = F(x) + pull(prev, cap)   (mesh.py:501); prev = prev_fn(x) if native.
+  // Then what the step kernels expect zeroed.
+  int begin() {
+    if (int rc = eval_prev()) return rc;
+    if (int rc = external_force()) return rc;
+    SFM_LAUNCH_NCOMP(force_kernel, p.ncomp, c.grid, kBlock, st, d->x, prev_ptr, d->a, p, cap0,
+                     p.has_prev);
+    if (c.small) {
+      sfm::prof_begin(sfm::kProfMesh, st);
+      SFM_LAUNCH_NCOMP(mesh_small_kernel, p.ncomp, 1, kBlock, st, d->x, d->v, d->a, prev_ptr, p,
+                       w.scal, cap0, w.partials, d->num_iters);
+      sfm::prof_end(sfm::kProfMesh, st);
+    }
+    if (c.fuse_target && w.target_list)
+      if (int rc = sfm::build_target_list(d->target, w.target_list, st)) return rc;
+    if (c.tiled) {
+      // LDS-tiled integrator (2-D): one launch per step, or advance + prev_fn +
+      // integrate when the spring targets depend on the advanced positions.
+      SFM_HIP_CHECK(hipMemsetAsync(w.ticket, 0, 2 * sizeof(int), st));
+      SFM_HIP_CHECK(hipMemsetAsync(w.tile_part, 0, (size_t)c.tiles.tiles * kNP * sizeof(u64), st));
+    }
+    if (p.fire && p.drift_cols) SFM_HIP_CHECK(hipMemsetAsync(w.col_ticket, 0, 4 * sizeof(int), st));
+    return SFM_OK;
   }
-  // default-link volumes: every spring once (integrate_march3d_kernel)
-  const March3dPlan march = (!tiled && !small) ? plan_march3d(p) : March3dPlan();
-  const int part_rows = march.T ? march.grid : grid;
-  // One integration step, enqueued on `ls`.
-  hipStream_t ls = st;
-#define SFM_STEP_DISPATCH(KERNEL, ...)                                       \
-  do {                                                                       \
-    if (p.ncomp == 2)                                                        \
-      hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(kBlock), 0, ls,         \
-                         __VA_ARGS__);                                       \
-    else                                                                     \
-      hipLaunchKernelGGL(KERNEL<3>, dim3(grid), dim3(kBlock), 0, ls,         \
-                         __VA_ARGS__);                                       \
-    SFM_LAUNCH_CHECK();                                                      \
-  } while (0)
-  // column means of the state in (xs, vs): ~16 rows per thread and chunk
-  const long long col_rows = p.N / p.X;
-  const int col_groups = p.X <= kBlock ? kBlock / p.X : 1;
-  const int col_chunks = static_cast<int>(std::max<long long>(
-      1, std::min<long long>(kColChunksMax, (col_rows + col_groups * 16LL - 1) / (col_groups * 16LL))));
-  const int col_rows_per = static_cast<int>((col_rows + col_chunks - 1) / col_chunks);
-  if (p.fire && p.drift_cols) SFM_HIP_CHECK(hipMemsetAsync(w.col_ticket, 0, 4 * sizeof(int), st));
-  auto column_means = [&](const float* xs, const float* vs) {
-    hipLaunchKernelGGL(drift_cols_kernel<3>, dim3(col_chunks, 3), dim3(kBlock), 0, ls, xs, vs, p,
-                       w.colsum, w.col_part, w.col_ticket, col_rows_per);
-  };
-  auto step = [&](int pending) -> int {
-    if (fused) {
-      float** bi = bufs[in];
-      float** bo = bufs[in ^ 1];
-      if (fuse_target) {
+
+  int tiled_launch(bool fused, float* const* bi, float* const* bo, int pending) {
+    sfm::prof_begin(sfm::kProfMesh, st);
+    const BandArgs ba = plain_band_args(c.tiles, c.xcd_map, c.pack);
+    if (fused)
+      hipLaunchKernelGGL(integrate_shared2d_kernel<true>, dim3(c.tgrid), dim3(kBlock), 0, st,
+                         bi[0], bi[1], bi[2], prev_ptr, bo[0], bo[1], bo[2], p, &w.scal[cur],
+                         &w.scal[cur ^ 1], cap0, w.tile_part, w.ticket, pending, c.tiles.nty,
+                         c.tiles.ntx, ba);
+    else
+      hipLaunchKernelGGL(integrate_shared2d_kernel<false>, dim3(c.tgrid), dim3(kBlock), 0, st,
+                         bi[0], bi[1], bi[2], prev_ptr, bo[0], bo[1], bo[2], p, &w.scal[cur],
+                         &w.scal[cur ^ 1], cap0, w.tile_part, w.ticket, pending, c.tiles.nty,
+                         c.tiles.ntx, ba);
+    sfm::prof_end(sfm::kProfMesh, st);
+    SFM_LAUNCH_CHECK();
+    if (p.fire) cur ^= 1;
+    return SFM_OK;
+  }
+
+  // One integration step.
+  int step(int pending) {
+    float* const own[3] = {d->x, d->v, d->a};
+    if (c.fused) {
+      float* const* bi = in ? w.alt : own;
+      float* const* bo = in ? own : w.alt;
+      if (c.fuse_target) {
         const sfm::AdvanceView av{bi[1], bi[2], &w.scal[cur], p.fire, pending,
                                   p.remove_drift, p.vv_dt, nullptr};
-        if (int rc = sfm::launch_target_mesh(d->target, bi[0], w.prev_buf, ls, &av, true,
+        if (int rc = sfm::launch_target_mesh(d->target, bi[0], w.prev_buf, st, &av, true,
                                              w.target_list))
           return rc;
       }
-      sfm::prof_begin(sfm::kProfMesh, ls);
-      hipLaunchKernelGGL(integrate_shared2d_kernel<true>, dim3(tgrid), dim3(kBlock), 0, ls,
-                         bi[0], bi[1], bi[2], prev_ptr, bo[0], bo[1], bo[2], p, &w.scal[cur],
-                         &w.scal[cur ^ 1], cap0, w.tile_part, w.ticket, pending, tiles.nty,
-                         tiles.ntx, plain_band_args(tiles, xcd_map, pack));
-      sfm::prof_end(sfm::kProfMesh, ls);
-      SFM_LAUNCH_CHECK();
       in ^= 1;
-      if (p.fire) cur ^= 1;
-    } else if (tiled) {
-      SFM_STEP_DISPATCH(advance_kernel, d->x, d->v, d->a, p, &w.scal[cur],
-                        &w.scal[cur ^ 1], w.partials, grid, pending ? 2 : 0, w.colsum);
-      cur ^= 1;
-      if (int rc = eval_prev(ls)) return rc;
-      sfm::prof_begin(sfm::kProfMesh, ls);
-      hipLaunchKernelGGL(integrate_shared2d_kernel<false>, dim3(tgrid), dim3(kBlock), 0, ls,
-                         d->x, d->v, d->a, prev_ptr, d->x, d->v, d->a, p, &w.scal[cur],
-                         &w.scal[cur ^ 1], cap0, w.tile_part, w.ticket, 1, tiles.nty,
-                         tiles.ntx, plain_band_args(tiles, xcd_map, pack));
-      sfm::prof_end(sfm::kProfMesh, ls);
-      SFM_LAUNCH_CHECK();
-      if (p.fire) cur ^= 1;
+      return tiled_launch(true, bi, bo, pending);
+    }
+    SFM_LAUNCH_NCOMP(advance_kernel, p.ncomp, c.grid, kBlock, st, d->x, d->v, d->a, p,
+                     &w.scal[cur], &w.scal[cur ^ 1], w.partials, c.part_rows,
+                     c.tiled && pending ? 2 : pending, w.colsum);
+    cur ^= 1;
+    if (int rc = eval_prev()) return rc;
+    if (c.tiled) return tiled_launch(false, own, own, 1);
+    if (int rc = external_force()) return rc;
+    sfm::prof_begin(sfm::kProfMesh, st);
+    if (c.march.T) {
+      if (int rc = launch_march3d(c.march, st, d->x, d->v, d->a, prev_ptr, p, &w.scal[cur], cap0,
+                                  w.partials))
+        return rc;
     } else {
-      SFM_STEP_DISPATCH(advance_kernel, d->x, d->v, d->a, p, &w.scal[cur],
-                        &w.scal[cur ^ 1], w.partials, part_rows, pending, w.colsum);
-      cur ^= 1;
-      if (int rc = eval_prev(ls)) return rc;
-      if (int rc = external_force()) return rc;
-      sfm::prof_begin(sfm::kProfMesh, ls);
-      if (march.T) {
-        if (int rc = launch_march3d(march, ls, d->x, d->v, d->a, prev_ptr, p, &w.scal[cur], cap0,
-                                    w.partials))
-          return rc;
-      } else {
-        SFM_STEP_DISPATCH(integrate_kernel, d->x, d->v, d->a, prev_ptr, p,
-                          &w.scal[cur], cap0, w.partials);
-      }
-      sfm::prof_end(sfm::kProfMesh, ls);
-      if (p.fire && p.drift_cols) {
-        column_means(d->x, d->v);
-        SFM_LAUNCH_CHECK();
-      }
+      SFM_LAUNCH_NCOMP(integrate_kernel, p.ncomp, c.grid, kBlock, st, d->x, d->v, d->a, prev_ptr,
+                       p, &w.scal[cur], cap0, w.partials);
+    }
+    sfm::prof_end(sfm::kProfMesh, st);
+    if (p.fire && p.drift_cols) {
+      hipLaunchKernelGGL(drift_cols_kernel<3>, dim3(col_chunks, 3), dim3(kBlock), 0, st, d->x,
+                         d->v, p, w.colsum, w.col_part, w.col_ticket, col_rows_per);
+      SFM_LAUNCH_CHECK();
     }
     return SFM_OK;
-  };
-#undef SFM_STEP_DISPATCH
+  }
 
-  int it = small ? d->num_iters : 0;
-  if (!small && d->num_iters > 0) {
-    if (int rc = step(0)) return rc;
-    it = 1;
+  int steps() {
+    for (int it = c.small ? d->num_iters : 0; it < d->num_iters; ++it)
+      if (int rc = step(it > 0)) return rc;
+    return SFM_OK;
   }
-  for (; it < d->num_iters; ++it)
-    if (int rc = step(1)) return rc;
-  if (in == 1) {
-    const size_t bytes = (size_t)p.ncomp * p.N * sizeof(float);
-    SFM_HIP_CHECK(hipMemcpyAsync(d->x, w.alt[0], bytes, hipMemcpyDeviceToDevice, st));
-    SFM_HIP_CHECK(hipMemcpyAsync(d->v, w.alt[1], bytes, hipMemcpyDeviceToDevice, st));
-    SFM_HIP_CHECK(hipMemcpyAsync(d->a, w.alt[2], bytes, hipMemcpyDeviceToDevice, st));
-  }
-  SFM_MESH_DISPATCH(finish_kernel, d->x, d->v, p, &w.scal[cur],
-                    &w.scal[cur ^ 1], w.partials, finish_mode == 1 ? part_rows : grid,
-                    finish_mode, w.stat_part, w.colsum);
-  cur ^= 1;
-#undef SFM_MESH_DISPATCH
-  hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, w.stat_part,
-                     grid, w.stats);
-  SFM_LAUNCH_CHECK();
 
-  Scalars s1;
-  float hs[2];
-  SFM_HIP_CHECK(hipMemcpyAsync(&s1, &w.scal[cur], sizeof(s1),
-                               hipMemcpyDeviceToHost, st));
-  SFM_HIP_CHECK(hipMemcpyAsync(hs, w.stats, sizeof(hs), hipMemcpyDeviceToHost, st));
-  SFM_HIP_CHECK(hipStreamSynchronize(st));
-  if (p.fire) {
-    fire->dt = s1.dt;
-    fire->alpha = s1.alpha;
-    fire->n_pos = s1.n_pos;
-    fire->cap = s1.cap;
+  // The state back in the caller's arrays, the pending gate / drift of the last
+  // step, the statistics.
+  int finish() {
+    if (in == 1) {
+      const size_t bytes = (size_t)p.ncomp * p.N * sizeof(float);
+      SFM_HIP_CHECK(hipMemcpyAsync(d->x, w.alt[0], bytes, hipMemcpyDeviceToDevice, st));
+      SFM_HIP_CHECK(hipMemcpyAsync(d->v, w.alt[1], bytes, hipMemcpyDeviceToDevice, st));
+      SFM_HIP_CHECK(hipMemcpyAsync(d->a, w.alt[2], bytes, hipMemcpyDeviceToDevice, st));
+    }
+    SFM_LAUNCH_NCOMP(finish_kernel, p.ncomp, c.grid, kBlock, st, d->x, d->v, p, &w.scal[cur],
+                     &w.scal[cur ^ 1], w.partials, c.finish_mode == 1 ? c.part_rows : c.grid,
+                     c.finish_mode, w.stat_part, w.colsum);
+    cur ^= 1;
+    hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, w.stat_part, c.grid, w.stats);
+    SFM_LAUNCH_CHECK();
+    return SFM_OK;
   }
-  stats->e_kin = hs[0];
-  stats->v_max = hs[1];
+};
+
+}  // namespace
+
+extern "C" {
+
+size_t sfm_mesh_workspace_bytes(const SfmMeshDesc* d) {
+  if (!d) return 0;
+  return carve_for(plan_chunk(d, nullptr), nullptr).bytes;
+}
+
+int sfm_mesh_force(const SfmMeshDesc* d, float* out) {
+  MeshParams p;
+  if (int rc = build_params(d, &p)) return rc;
+  if (!d->x || !out) return sfm::fail(SFM_ERR_INVALID, "x/out is NULL");
+  if (p.force_kind == SFM_FORCE_EXTERNAL)
+    return sfm::fail(SFM_ERR_INVALID, "sfm_mesh_force: the external force is the caller's");
+  SFM_LAUNCH_NCOMP(force_kernel, p.ncomp, grid_for(p.N), kBlock, static_cast<hipStream_t>(d->stream),
+                   d->x, nullptr, out, p, 0.f, 0);
   return SFM_OK;
+}
+
+int sfm_mesh_relax_chunk(const SfmMeshDesc* d, SfmFireState* fire,
+                         SfmChunkStats* stats) {
+  MeshParams p;
+  if (int rc = build_params(d, &p)) return rc;
+  if (int rc = validate_chunk(d, fire, stats)) return rc;
+  const ChunkPlan plan = plan_chunk(d, &p);
+  const MeshWorkspace w = carve_for(plan, d->workspace);
+  if (!d->workspace || d->workspace_bytes < w.bytes)
+    return sfm::fail(SFM_ERR_WORKSPACE, "mesh workspace needs %zu bytes, got %zu",
+                     w.bytes, d->workspace_bytes);
+  ChunkRun run(d, p, plan, w, *fire);
+  if (int rc = run.write_scalars()) return rc;
+  if (plan.persist_tile) {
+    bool done = false;
+    if (int rc = run.persistent(fire, stats, &done)) return rc;
+    if (done) return SFM_OK;
+  }
+  if (int rc = run.begin()) return rc;
+  if (int rc = run.steps()) return rc;
+  if (int rc = run.finish()) return rc;
+  return read_back(run.st, &w.scal[run.cur], w.stats, p.fire, fire, stats);
 }
 
 // ---------------------------------------------------------------------------
@@ -3799,7 +3801,7 @@ shard_sums_kernel(const float* __restrict__ partials, int rows, float* __restric
 }
 
 int shard_setup(const SfmMeshDesc* d, const SfmMeshShard* sh, MeshParams* p,
-                MeshWorkspace* w) {
+                MeshWorkspace* w, TilePlan* tiles = nullptr) {
   if (int rc = build_params(d, p)) return rc;
   if (!sh) return sfm::fail(SFM_ERR_INVALID, "shard is NULL");
   if (!d->x || !d->v || !d->a)
@@ -3818,23 +3820,14 @@ int shard_setup(const SfmMeshDesc* d, const SfmMeshShard* sh, MeshParams* p,
   p->own_y0 = sh->own_y0;
   p->own_y1 = sh->own_y1;
   p->n_f = static_cast<float>(sh->global_nodes);
-  *w = carve_for(d, d->workspace, nullptr);
+  const ChunkPlan plan = plan_chunk(d, nullptr);   // the workspace and its tile plan
+  if (tiles) *tiles = plan.tiles;
+  *w = carve_for(plan, d->workspace);
   if (!d->workspace || d->workspace_bytes < w->bytes)
     return sfm::fail(SFM_ERR_WORKSPACE, "mesh workspace needs %zu bytes, got %zu",
                      w->bytes, d->workspace_bytes);
   return SFM_OK;
 }
-
-#define SFM_SHARD_DISPATCH(KERNEL, ...)                                      \
-  do {                                                                       \
-    if (p.ncomp == 2)                                                        \
-      hipLaunchKernelGGL(KERNEL<2>, dim3(grid), dim3(kBlock), 0, st,         \
-                         __VA_ARGS__);                                       \
-    else                                                                     \
-      hipLaunchKernelGGL(KERNEL<3>, dim3(grid), dim3(kBlock), 0, st,         \
-                         __VA_ARGS__);                                       \
-    SFM_LAUNCH_CHECK();                                                      \
-  } while (0)
 
 }  // namespace
 
@@ -3845,20 +3838,14 @@ int sfm_mesh_shard_begin(const SfmMeshDesc* d, SfmMeshShard* sh,
   if (int rc = shard_setup(d, sh, &p, &w)) return rc;
   if (!fire) return sfm::fail(SFM_ERR_INVALID, "fire is NULL");
   hipStream_t st = static_cast<hipStream_t>(d->stream);
-  const int grid = grid_for(p.N);
-  Scalars s0;
-  std::memset(&s0, 0, sizeof(s0));
-  s0.dt = fire->dt;
-  s0.alpha = fire->alpha;
-  s0.n_pos = 0;
-  s0.cap = fire->cap;
-  s0.gate = 1.f;
+  const Scalars s0 = initial_scalars(*fire);
   SFM_HIP_CHECK(hipMemcpyAsync(&w.scal[0], &s0, sizeof(s0), hipMemcpyHostToDevice, st));
   sh->phase = 0;
   sh->cap0 = fire->cap;
   // a = F(x) + pull(prev, cap) on every local row; the halo rows' values are
   // replaced by the owners' at the first exchange
-  SFM_SHARD_DISPATCH(force_kernel, d->x, d->prev, d->a, p, fire->cap, p.has_prev);
+  SFM_LAUNCH_NCOMP(force_kernel, p.ncomp, grid_for(p.N), kBlock, st, d->x, d->prev, d->a, p,
+                   fire->cap, p.has_prev);
   return SFM_OK;
 }
 
@@ -3867,11 +3854,10 @@ int sfm_mesh_shard_advance(const SfmMeshDesc* d, SfmMeshShard* sh) {
   MeshWorkspace w;
   if (int rc = shard_setup(d, sh, &p, &w)) return rc;
   hipStream_t st = static_cast<hipStream_t>(d->stream);
-  const int grid = grid_for(p.N);
   const int cur = sh->phase & 1;
   const int pending = sh->phase > 0 ? 1 : 0;
-  SFM_SHARD_DISPATCH(advance_kernel, d->x, d->v, d->a, p, &w.scal[cur], &w.scal[cur ^ 1],
-                     sh->sums, sh->n_ranks, pending, w.colsum);
+  SFM_LAUNCH_NCOMP(advance_kernel, p.ncomp, grid_for(p.N), kBlock, st, d->x, d->v, d->a, p,
+                   &w.scal[cur], &w.scal[cur ^ 1], sh->sums, sh->n_ranks, pending, w.colsum);
   sh->phase += 1;
   return SFM_OK;
 }
@@ -3884,8 +3870,8 @@ int sfm_mesh_shard_integrate(const SfmMeshDesc* d, SfmMeshShard* sh) {
   const int grid = grid_for(p.N);
   const int cur = sh->phase & 1;
   sfm::prof_begin(sfm::kProfMesh, st);
-  SFM_SHARD_DISPATCH(integrate_kernel, d->x, d->v, d->a, d->prev, p, &w.scal[cur],
-                     sh->cap0, w.partials);
+  SFM_LAUNCH_NCOMP(integrate_kernel, p.ncomp, grid, kBlock, st, d->x, d->v, d->a, d->prev, p,
+                   &w.scal[cur], sh->cap0, w.partials);
   sfm::prof_end(sfm::kProfMesh, st);
   if (p.fire) {
     hipLaunchKernelGGL(shard_sums_kernel, dim3(1), dim3(kBlock), 0, st, w.partials, grid,
@@ -3903,30 +3889,16 @@ int sfm_mesh_shard_finish(const SfmMeshDesc* d, SfmMeshShard* sh, SfmFireState* 
   if (!fire || !stats) return sfm::fail(SFM_ERR_INVALID, "fire/stats is NULL");
   hipStream_t st = static_cast<hipStream_t>(d->stream);
   const int grid = grid_for(p.N);
-  int cur = sh->phase & 1;
+  const int cur = sh->phase & 1;
   const int pending = sh->phase > 0 ? 1 : 0;
-  SFM_SHARD_DISPATCH(finish_kernel, d->x, d->v, p, &w.scal[cur], &w.scal[cur ^ 1],
-                     sh->sums, sh->n_ranks, pending, w.stat_part, w.colsum);
-  cur ^= 1;
+  SFM_LAUNCH_NCOMP(finish_kernel, p.ncomp, grid, kBlock, st, d->x, d->v, p, &w.scal[cur],
+                   &w.scal[cur ^ 1], sh->sums, sh->n_ranks, pending, w.stat_part, w.colsum);
   hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, w.stat_part, grid,
                      w.stats);
   SFM_LAUNCH_CHECK();
-  Scalars s1;
-  float hs[2];
-  SFM_HIP_CHECK(hipMemcpyAsync(&s1, &w.scal[cur], sizeof(s1), hipMemcpyDeviceToHost, st));
-  SFM_HIP_CHECK(hipMemcpyAsync(hs, w.stats, sizeof(hs), hipMemcpyDeviceToHost, st));
-  SFM_HIP_CHECK(hipStreamSynchronize(st));
-  if (p.fire) {
-    fire->dt = s1.dt;
-    fire->alpha = s1.alpha;
-    fire->n_pos = s1.n_pos;
-    fire->cap = s1.cap;
-  }
-  stats->e_kin = hs[0];   // of the owned rows: the caller adds the bands up
-  stats->v_max = hs[1];   // max over the owned rows
-  return SFM_OK;
+  // e_kin of the owned rows (the caller adds the bands up), v_max over the owned rows
+  return read_back(st, &w.scal[cur ^ 1], w.stats, p.fire, fire, stats);
 }
-#undef SFM_SHARD_DISPATCH
 
 }  // extern "C"
 
@@ -4004,118 +3976,149 @@ void launch_rows(const RowJobs& jobs, hipStream_t st) {
   hipLaunchKernelGGL(band_rows_kernel, dim3(gx, 3, jobs.n), dim3(kBlock), 0, st, jobs);
 }
 
-}  // namespace
+struct EventGuard {
+  hipEvent_t* e[3];
+  ~EventGuard() { for (auto p : e) if (*p) (void)hipEventDestroy(*p); }
+};
+// An error return between a fork (the exchange stream waits for the main
+// stream) and its join must not leave the exchange stream running behind the
+// caller's back: the guard joins it into the main stream on the way out.
+struct JoinGuard {
+  hipStream_t st, xs;
+  hipEvent_t* ev;
+  bool forked;
+  ~JoinGuard() {
+    if (forked && *ev && hipEventRecord(*ev, xs) == hipSuccess) (void)hipStreamWaitEvent(st, *ev, 0);
+  }
+};
 
-extern "C" {
-
-size_t sfm_mesh_banded_scratch_bytes(const SfmBandedDesc* b) {
-  if (!b || !b->bands || b->n_local < 1) return 0;
-  const SfmMeshDesc& d = b->bands[0];
-  const size_t row = 3 * (size_t)d.ncomp * d.shape[0] * d.shape[1] * d.shape[3];
-  sfm::Carver c(nullptr);
-  const size_t total = (size_t)std::max(b->n_ranks, 1) * b->n_local;
-  c.take<float>(2 * total * kNP);      // sums of all bands, double buffered by step parity
-  c.take<float>(total * 2);            // e_kin, v_max of all bands
-  c.take<BandDev>(2 * (size_t)b->n_local);  // multi-band launch tables (two parities)
-  for (int i = 0; i < b->n_local; ++i)
-    for (int k = 0; k < 4; ++k) c.take<float>(row);
-  return c.total();
-}
-
-int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkStats* stats) {
-  if (!b || !b->bands || !b->shards || !fire || !stats)
-    return sfm::fail(SFM_ERR_INVALID, "banded: NULL argument");
-  const int nl = b->n_local;
-  const int n_ranks = std::max(b->n_ranks, 1);
-  if (nl < 1 || nl > kMaxLocalBands)
-    return sfm::fail(SFM_ERR_INVALID, "banded: 1..%d bands per rank", kMaxLocalBands);
-  if (b->rank < 0 || b->rank >= n_ranks) return sfm::fail(SFM_ERR_INVALID, "banded: rank");
-  // host-staged transport: the inter-rank branch without RCCL peers
-  const bool host_x = !b->comm && n_ranks > 1 && b->host_halo && b->host_allgather;
-  if (n_ranks > 1 && !b->comm && !host_x)
-    return sfm::fail(SFM_ERR_INVALID,
-                     "banded: %d ranks need a communicator or the host_halo / host_allgather pair",
-                     n_ranks);
-  const bool transport = b->comm != nullptr || host_x;
-  const bool loopback = (b->flags & SFM_BANDED_LOOPBACK) != 0;
-  if (loopback && !b->comm)
-    return sfm::fail(SFM_ERR_INVALID, "banded: loop-back needs a communicator");
-  if (b->comm && (sfm::comm_size(b->comm) != n_ranks || sfm::comm_rank(b->comm) != b->rank))
-    return sfm::fail(SFM_ERR_INVALID, "banded: communicator is rank %d of %d, desc says %d of %d",
-                     sfm::comm_rank(b->comm), sfm::comm_size(b->comm), b->rank, n_ranks);
-  const int total = n_ranks * nl;
-  if (total > kMaxBlocks) return sfm::fail(SFM_ERR_INVALID, "banded: too many bands");
-  const SfmMeshDesc& d0 = b->bands[0];
-  hipStream_t st = static_cast<hipStream_t>(d0.stream);
-  hipStream_t xs = b->comm_stream ? static_cast<hipStream_t>(b->comm_stream) : st;
-  const int iters = d0.num_iters;
-  if (iters < 0) return sfm::fail(SFM_ERR_INVALID, "num_iters < 0");
-
+// One call of sfm_mesh_relax_banded.  (Lives on the caller's stack: the launch
+// tables and the start scalars are sources of asynchronous copies.)
+struct BandedRun {
+  const SfmBandedDesc* b;
+  const SfmMeshDesc& d0;
+  const int nl, n_ranks, total;
+  const bool host_x;     // host-staged transport: the inter-rank branch without RCCL peers
+  const bool transport, loopback;
+  const hipStream_t st, xs;
+  const int iters;
+  const int C, planes, X;
+  const size_t row_floats, cnt;   // one row of one array; of (x, v, a)
   // scratch
-  const size_t need = sfm_mesh_banded_scratch_bytes(b);
-  if (!b->scratch || b->scratch_bytes < need)
-    return sfm::fail(SFM_ERR_WORKSPACE, "banded scratch needs %zu bytes, got %zu", need,
-                     b->scratch_bytes);
-  sfm::Carver carve_s(b->scratch);
+  float* sums_buf = nullptr;
+  float* stats_all = nullptr;
+  BandDev* band_dev[2] = {nullptr, nullptr};
+  BandState bs[kMaxLocalBands];
+  bool fused = true, overlap = false;
+  RowJobs before[2], after[2];
+  int grid_mode[3] = {0, 0, 0};
+  BandDev host[2][kMaxLocalBands];
+  // Host staging of the transport callbacks (pageable memory: the copies return
+  // when they are done).  Parts: send lo, send hi, recv lo, recv hi.
+  std::vector<float> stage_rows, stage_gather;
+  Scalars s0;
+  float cap0 = 0.f;
+  int in = 0, cur = 0;
+  const int xcd_tri;   // SFM_MESH_XCD
+  hipEvent_t ev_edge = nullptr, ev_int = nullptr, ev_x = nullptr;
+  EventGuard guard{{&ev_edge, &ev_int, &ev_x}};
+  JoinGuard join;
+
+  explicit BandedRun(const SfmBandedDesc* b_)
+      : b(b_), d0(b_->bands[0]), nl(b_->n_local), n_ranks(std::max(b_->n_ranks, 1)),
+        total(n_ranks * nl),
+        host_x(!b_->comm && n_ranks > 1 && b_->host_halo && b_->host_allgather),
+        transport(b_->comm != nullptr || host_x),
+        loopback((b_->flags & SFM_BANDED_LOOPBACK) != 0),
+        st(static_cast<hipStream_t>(d0.stream)),
+        xs(b_->comm_stream ? static_cast<hipStream_t>(b_->comm_stream) : st),
+        iters(d0.num_iters), C(d0.ncomp), planes(d0.shape[0] * d0.shape[1]), X(d0.shape[3]),
+        row_floats((size_t)d0.ncomp * d0.shape[0] * d0.shape[1] * d0.shape[3]),
+        cnt(3 * row_floats), xcd_tri(sfm::option_tri("SFM_MESH_XCD")),
+        join{st, xs, &ev_x, false} {}
+  BandedRun(const BandedRun&) = delete;
+
   // Partial sums of all bands, one buffer per step parity: a band's kernel of
   // step k leaves its sums while a later band's kernel of the same step still
   // reads the sums of step k - 1.
-  float* sums_buf = carve_s.take<float>((size_t)2 * total * kNP);
-  auto sums_of = [&](int step) { return sums_buf + (size_t)(step & 1) * total * kNP; };
-  float* stats_all = carve_s.take<float>((size_t)total * 2);
-  BandDev* band_dev_all = carve_s.take<BandDev>(2 * (size_t)nl);
-  BandDev* band_dev[2] = {band_dev_all, band_dev_all + nl};
-  const size_t row_floats = (size_t)d0.ncomp * d0.shape[0] * d0.shape[1] * d0.shape[3];
+  float* sums_of(int step) const { return sums_buf + (size_t)(step & 1) * total * kNP; }
 
-  BandState bs[kMaxLocalBands];
-  bool fused = true;
-  for (int i = 0; i < nl; ++i) {
-    const SfmMeshDesc& d = b->bands[i];
-    SfmMeshShard& sh = b->shards[i];
-    if (d.stream != d0.stream || d.num_iters != iters || d.ncomp != d0.ncomp ||
-        d.shape[0] != d0.shape[0] || d.shape[1] != d0.shape[1] || d.shape[3] != d0.shape[3] ||
-        d.fire != d0.fire || d.remove_drift != d0.remove_drift)
-      return sfm::fail(SFM_ERR_INVALID, "banded: the bands of a mesh share shape and config");
-    const int g = b->rank * nl + i;
-    sh.n_ranks = total;
-    sh.sums = sums_buf;
-    sh.my_sums = sums_buf + (size_t)g * kNP;
-    BandState& s = bs[i];
-    if (int rc = shard_setup(&d, &sh, &s.p, &s.w)) return rc;
-    s.w = carve_for(&d, d.workspace, &s.tiles);
-    s.grid = grid_for(s.p.N);
-    s.has_lo = g > 0;
-    s.has_hi = g < total - 1;
-    if (s.has_lo != (sh.own_y0 > 0) || s.has_hi != (sh.own_y1 < s.p.Y) ||
-        sh.own_y0 > 1 || s.p.Y - sh.own_y1 > 1)
+  int validate() const {
+    if (b->rank < 0 || b->rank >= n_ranks) return sfm::fail(SFM_ERR_INVALID, "banded: rank");
+    if (n_ranks > 1 && !b->comm && !host_x)
       return sfm::fail(SFM_ERR_INVALID,
-                       "banded: band %d of %d owns rows [%d, %d) of %d: one halo row per "
-                       "existing neighbour", g, total, sh.own_y0, sh.own_y1, s.p.Y);
-    for (int k = 0; k < 4; ++k) s.buf[k] = carve_s.take<float>(3 * row_floats);
-    s.set[0][0] = d.x;
-    s.set[0][1] = d.v;
-    s.set[0][2] = d.a;
-    for (int k = 0; k < 3; ++k) s.set[1][k] = s.w.alt[k];
-    fused = fused && s.p.ncomp == 2 && s.p.force_kind == SFM_FORCE_SPRINGS &&
-            s.tiles.tx == kSX && s.w.alt[0] != nullptr;
+                       "banded: %d ranks need a communicator or the host_halo / host_allgather pair",
+                       n_ranks);
+    if (loopback && !b->comm)
+      return sfm::fail(SFM_ERR_INVALID, "banded: loop-back needs a communicator");
+    if (b->comm && (sfm::comm_size(b->comm) != n_ranks || sfm::comm_rank(b->comm) != b->rank))
+      return sfm::fail(SFM_ERR_INVALID, "banded: communicator is rank %d of %d, desc says %d of %d",
+                       sfm::comm_rank(b->comm), sfm::comm_size(b->comm), b->rank, n_ranks);
+    if (total > kMaxBlocks) return sfm::fail(SFM_ERR_INVALID, "banded: too many bands");
+    if (iters < 0) return sfm::fail(SFM_ERR_INVALID, "num_iters < 0");
+    const size_t need = sfm_mesh_banded_scratch_bytes(b);
+    if (!b->scratch || b->scratch_bytes < need)
+      return sfm::fail(SFM_ERR_WORKSPACE, "banded scratch needs %zu bytes, got %zu", need,
+                       b->scratch_bytes);
+    return SFM_OK;
   }
-  // The second stream pays for itself only when edge rows really travel (RCCL):
-  // between bands of one process the exchange is one small copy kernel.
-  const bool overlap = fused && xs != st && transport && !(b->flags & SFM_BANDED_NO_OVERLAP);
-  const int C = d0.ncomp;
-  const int planes = d0.shape[0] * d0.shape[1], X = d0.shape[3];
 
-  // Row jobs of one exchange on buffer set `q`: `before` runs ahead of the RCCL
-  // group (local copies + packing), `after` behind it (unpacking).
-  auto array_side = [&](RowJob* j, bool src, const BandState& s, int q, int row) {
+  // Scratch, and per local band: params, workspace, tile plan, buffers.
+  int setup_bands() {
+    sfm::Carver carve_s(b->scratch);
+    sums_buf = carve_s.take<float>((size_t)2 * total * kNP);
+    stats_all = carve_s.take<float>((size_t)total * 2);
+    band_dev[0] = carve_s.take<BandDev>(2 * (size_t)nl);
+    band_dev[1] = band_dev[0] + nl;
+    for (int i = 0; i < nl; ++i) {
+      const SfmMeshDesc& d = b->bands[i];
+      SfmMeshShard& sh = b->shards[i];
+      if (d.stream != d0.stream || d.num_iters != iters || d.ncomp != d0.ncomp ||
+          d.shape[0] != d0.shape[0] || d.shape[1] != d0.shape[1] || d.shape[3] != d0.shape[3] ||
+          d.fire != d0.fire || d.remove_drift != d0.remove_drift)
+        return sfm::fail(SFM_ERR_INVALID, "banded: the bands of a mesh share shape and config");
+      const int g = b->rank * nl + i;
+      sh.n_ranks = total;
+      sh.sums = sums_buf;
+      sh.my_sums = sums_buf + (size_t)g * kNP;
+      BandState& s = bs[i];
+      if (int rc = shard_setup(&d, &sh, &s.p, &s.w, &s.tiles)) return rc;
+      s.grid = grid_for(s.p.N);
+      s.has_lo = g > 0;
+      s.has_hi = g < total - 1;
+      if (s.has_lo != (sh.own_y0 > 0) || s.has_hi != (sh.own_y1 < s.p.Y) ||
+          sh.own_y0 > 1 || s.p.Y - sh.own_y1 > 1)
+        return sfm::fail(SFM_ERR_INVALID,
+                         "banded: band %d of %d owns rows [%d, %d) of %d: one halo row per "
+                         "existing neighbour", g, total, sh.own_y0, sh.own_y1, s.p.Y);
+      for (int k = 0; k < 4; ++k) s.buf[k] = carve_s.take<float>(3 * row_floats);
+      s.set[0][0] = d.x;
+      s.set[0][1] = d.v;
+      s.set[0][2] = d.a;
+      for (int k = 0; k < 3; ++k) s.set[1][k] = s.w.alt[k];
+      fused = fused && s.p.ncomp == 2 && s.p.force_kind == SFM_FORCE_SPRINGS &&
+              s.tiles.tx == kSX && s.w.alt[0] != nullptr;
+    }
+    // The second stream pays for itself only when edge rows really travel (RCCL):
+    // between bands of one process the exchange is one small copy kernel.
+    overlap = fused && xs != st && transport && !(b->flags & SFM_BANDED_NO_OVERLAP);
+    if (host_x) {
+      stage_rows.resize(4 * cnt);
+      stage_gather.resize((size_t)total * std::max<size_t>(kNP, 2));
+    }
+    return SFM_OK;
+  }
+
+  // -- row jobs ---------------------------------------------------------------
+  void array_side(RowJob* j, bool src, const BandState& s, int q, int row) const {
     for (int k = 0; k < 3; ++k) {
       if (src) j->src[k] = s.set[q][k]; else j->dst[k] = s.set[q][k];
     }
     const long long n = s.p.N, pl = (long long)s.p.Y * X, off = (long long)row * X;
     if (src) { j->src_n = n; j->src_plane = pl; j->src_off = off; }
     else { j->dst_n = n; j->dst_plane = pl; j->dst_off = off; }
-  };
-  auto buffer_side = [&](RowJob* j, bool src, float* buf) {
+  }
+  void buffer_side(RowJob* j, bool src, float* buf) const {
     for (int k = 0; k < 3; ++k) {
       float* base = buf + (size_t)k * row_floats;
       if (src) j->src[k] = base; else j->dst[k] = base;
@@ -4123,12 +4126,16 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
     const long long n = (long long)planes * X;
     if (src) { j->src_n = n; j->src_plane = X; j->src_off = 0; }
     else { j->dst_n = n; j->dst_plane = X; j->dst_off = 0; }
-  };
-  auto build_jobs = [&](int q, RowJobs* before, RowJobs* after) {
-    before->n = after->n = 0;
-    before->ncomp = after->ncomp = C;
-    before->planes = after->planes = planes;
-    before->X = after->X = X;
+  }
+  // Row jobs of one exchange on buffer set `q`: `before` runs ahead of the RCCL
+  // group (local copies + packing), `after` behind it (unpacking).
+  void build_jobs(int q) {
+    RowJobs* bf = &before[q];
+    RowJobs* af = &after[q];
+    bf->n = af->n = 0;
+    bf->ncomp = af->ncomp = C;
+    bf->planes = af->planes = planes;
+    bf->X = af->X = X;
     for (int i = 0; i < nl; ++i) {
       BandState& s = bs[i];
       const SfmMeshShard& sh = b->shards[i];
@@ -4137,40 +4144,36 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
       if (s.has_hi && !hi_remote) {
         // local pair (i, i + 1): my last owned row -> its low halo row and back
         BandState& t = bs[i + 1];
-        RowJob* j = &before->job[before->n++];
+        RowJob* j = &bf->job[bf->n++];
         array_side(j, true, s, q, sh.own_y1 - 1);
         array_side(j, false, t, q, b->shards[i + 1].own_y0 - 1);
-        j = &before->job[before->n++];
+        j = &bf->job[bf->n++];
         array_side(j, true, t, q, b->shards[i + 1].own_y0);
         array_side(j, false, s, q, sh.own_y1);
       }
       if (lo_remote) {
-        RowJob* j = &before->job[before->n++];
+        RowJob* j = &bf->job[bf->n++];
         array_side(j, true, s, q, sh.own_y0);
         buffer_side(j, false, s.buf[0]);
-        j = &after->job[after->n++];
+        j = &af->job[af->n++];
         buffer_side(j, true, s.buf[2]);
         array_side(j, false, s, q, sh.own_y0 - 1);
       }
       if (hi_remote) {
-        RowJob* j = &before->job[before->n++];
+        RowJob* j = &bf->job[bf->n++];
         array_side(j, true, s, q, sh.own_y1 - 1);
         buffer_side(j, false, s.buf[1]);
-        j = &after->job[after->n++];
+        j = &af->job[af->n++];
         buffer_side(j, true, s.buf[3]);
         array_side(j, false, s, q, sh.own_y1);
       }
     }
-  };
-  RowJobs before[2], after[2];
-  build_jobs(0, &before[0], &after[0]);
-  if (fused) build_jobs(1, &before[1], &after[1]);
+  }
 
+  // -- launch tables ------------------------------------------------------------
   // Multi-band launch tables of the fused step, one per parity q of the input
   // set (the scalars and the sums buffers alternate with it).
-  int grid_mode[3] = {0, 0, 0};
-  BandDev host[2][kMaxLocalBands];   // (function scope: source of async copies)
-  if (fused) {
+  int upload_tables() {
     std::memset(host, 0, sizeof(host));
     int base[3] = {0, 0, 0};
     for (int i = 0; i < nl; ++i) {
@@ -4226,25 +4229,14 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
       for (int m = 0; m < 3; ++m) base[m] += count[m];
     }
     for (int m = 0; m < 3; ++m) grid_mode[m] = base[m];
-    SFM_HIP_CHECK(hipMemcpyAsync(band_dev[0], host[0], sizeof(BandDev) * nl,
-                                 hipMemcpyHostToDevice, st));
-    SFM_HIP_CHECK(hipMemcpyAsync(band_dev[1], host[1], sizeof(BandDev) * nl,
-                                 hipMemcpyHostToDevice, st));
+    for (int q = 0; q < 2; ++q)
+      SFM_HIP_CHECK(hipMemcpyAsync(band_dev[q], host[q], sizeof(BandDev) * nl,
+                                   hipMemcpyHostToDevice, st));
+    return SFM_OK;
   }
 
-  // The grouped point-to-point part of one exchange.  Between ranks: the first
-  // band's low edge <-> rank - 1, the last band's high edge <-> rank + 1.  Loop
-  // back (tests on one GPU): every edge between local bands travels through a
-  // self send / recv -- sends and receives to the same peer match in order.
-  const size_t cnt = 3 * row_floats;
-  // Host staging of the transport callbacks (pageable memory: the copies return
-  // when they are done).  Parts: send lo, send hi, recv lo, recv hi.
-  std::vector<float> stage_rows, stage_gather;
-  if (host_x) {
-    stage_rows.resize(4 * cnt);
-    stage_gather.resize((size_t)total * std::max<size_t>(kNP, 2));
-  }
-  auto host_p2p = [&](hipStream_t s_) -> int {
+  // -- transport ----------------------------------------------------------------
+  int host_p2p(hipStream_t s_) {
     const bool lo = bs[0].has_lo && b->rank > 0;
     const bool hi = bs[nl - 1].has_hi && b->rank < n_ranks - 1;
     if (!lo && !hi) return SFM_OK;
@@ -4259,9 +4251,9 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
     if (hi) SFM_HIP_CHECK(hipMemcpyAsync(bs[nl - 1].buf[3], h + 3 * cnt, cnt * sizeof(float), hipMemcpyHostToDevice, s_));
     SFM_HIP_CHECK(hipStreamSynchronize(s_));   // the staging area is reused
     return SFM_OK;
-  };
+  }
   // recv[r * count ..) = the `count` floats at recv + rank * count of rank r (in place)
-  auto allgather = [&](float* recv, size_t count, hipStream_t s_) -> int {
+  int allgather(float* recv, size_t count, hipStream_t s_) {
     if (b->comm) return sfm_comm_allgather(b->comm, recv + (size_t)b->rank * count, recv, count, s_);
     float* h = stage_gather.data();
     SFM_HIP_CHECK(hipMemcpyAsync(h + (size_t)b->rank * count, recv + (size_t)b->rank * count,
@@ -4272,8 +4264,12 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
     SFM_HIP_CHECK(hipMemcpyAsync(recv, h, (size_t)n_ranks * count * sizeof(float), hipMemcpyHostToDevice, s_));
     SFM_HIP_CHECK(hipStreamSynchronize(s_));
     return SFM_OK;
-  };
-  auto p2p = [&](hipStream_t s_) -> int {
+  }
+  // The grouped point-to-point part of one exchange.  Between ranks: the first
+  // band's low edge <-> rank - 1, the last band's high edge <-> rank + 1.  Loop
+  // back (tests on one GPU): every edge between local bands travels through a
+  // self send / recv -- sends and receives to the same peer match in order.
+  int p2p(hipStream_t s_) {
     if (host_x) return host_p2p(s_);
     if (!b->comm) return SFM_OK;
     bool any = false;
@@ -4301,71 +4297,29 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
       }
     }
     return sfm::comm_group_end(b->comm, rc);
-  };
-  auto exchange = [&](int q, hipStream_t s_) -> int {
+  }
+  int exchange(int q, hipStream_t s_) {
     launch_rows(before[q], s_);
     SFM_LAUNCH_CHECK();
+    return exchange_after(q, s_);
+  }
+  // (the fused step leaves its edge rows in the send buffers itself)
+  int exchange_after(int q, hipStream_t s_) {
     if (int rc = p2p(s_)) return rc;
     launch_rows(after[q], s_);
     SFM_LAUNCH_CHECK();
     return SFM_OK;
-  };
-  auto gather_sums = [&](int step, hipStream_t s_) -> int {
+  }
+  int gather_sums(int step, hipStream_t s_) {
+    if (!d0.fire) return SFM_OK;
     if (n_ranks == 1 && !loopback) return SFM_OK;   // my_sums are rows of the buffer already
     // in place: this rank's rows sit at their final position
     return allgather(sums_of(step), (size_t)nl * kNP, s_);
-  };
-
-  hipEvent_t ev_edge = nullptr, ev_int = nullptr, ev_x = nullptr;
-  struct EventGuard {
-    hipEvent_t* e[3];
-    ~EventGuard() { for (auto p : e) if (*p) (void)hipEventDestroy(*p); }
-  } guard{{&ev_edge, &ev_int, &ev_x}};
-  if (overlap) {
-    SFM_HIP_CHECK(hipEventCreateWithFlags(&ev_edge, hipEventDisableTiming));
-    SFM_HIP_CHECK(hipEventCreateWithFlags(&ev_int, hipEventDisableTiming));
-    SFM_HIP_CHECK(hipEventCreateWithFlags(&ev_x, hipEventDisableTiming));
-  }
-  // An error return between a fork (the exchange stream waits for the main
-  // stream) and its join must not leave the exchange stream running behind the
-  // caller's back: the guard joins it into the main stream on the way out.
-  struct JoinGuard {
-    hipStream_t st, xs;
-    hipEvent_t* ev;
-    bool forked;
-    ~JoinGuard() {
-      if (forked && *ev && hipEventRecord(*ev, xs) == hipSuccess) (void)hipStreamWaitEvent(st, *ev, 0);
-    }
-  } join{st, xs, &ev_x, false};
-
-  // -- begin: scalars, a = F(x) + pull on the local rows of every band --------
-  Scalars s0;
-  std::memset(&s0, 0, sizeof(s0));
-  s0.dt = fire->dt;
-  s0.alpha = fire->alpha;
-  s0.n_pos = 0;
-  s0.cap = fire->cap;
-  s0.gate = 1.f;
-  const float cap0 = fire->cap;
-  for (int i = 0; i < nl; ++i) {
-    BandState& s = bs[i];
-    const SfmMeshDesc& d = b->bands[i];
-    SFM_HIP_CHECK(hipMemcpyAsync(&s.w.scal[0], &s0, sizeof(s0), hipMemcpyHostToDevice, st));
-    if (fused) {
-      SFM_HIP_CHECK(hipMemsetAsync(s.w.ticket, 0, 2 * sizeof(int), st));
-      SFM_HIP_CHECK(hipMemsetAsync(s.w.tile_part, 0, (size_t)s.tiles.tiles * kNP * sizeof(u64), st));
-    }
-    if (s.p.ncomp == 2)
-      hipLaunchKernelGGL(force_kernel<2>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.prev, d.a,
-                         s.p, cap0, s.p.has_prev);
-    else
-      hipLaunchKernelGGL(force_kernel<3>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.prev, d.a,
-                         s.p, cap0, s.p.has_prev);
-    SFM_LAUNCH_CHECK();
   }
   // Everything that touches the communicator runs on the comm stream when there
   // is one (fork from / join into the main stream around `fn`).
-  auto on_comm_stream = [&](auto fn) -> int {
+  template <typename Fn>
+  int on_comm_stream(Fn fn) {
     if (!overlap) return fn(st);
     SFM_HIP_CHECK(hipEventRecord(ev_int, st));
     SFM_HIP_CHECK(hipStreamWaitEvent(xs, ev_int, 0));
@@ -4375,169 +4329,192 @@ int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkSt
     SFM_HIP_CHECK(hipStreamWaitEvent(st, ev_x, 0));
     join.forked = false;
     return SFM_OK;
-  };
-  // the halo rows' a (and, from the second chunk on, nothing else) is stale
-  if (int rc = on_comm_stream([&](hipStream_t s_) { return exchange(0, s_); })) return rc;
+  }
 
-  int xcd_opt = -1;   // SFM_MESH_XCD: 0 off, 1 from 64 tiles on, default from 2048 on
-  {
-    const std::string xo = sfm::option_str("SFM_MESH_XCD");
-    if (!xo.empty() && (xo[0] == '0' || xo[0] == '1')) xcd_opt = xo[0] - '0';
-  }
-  int in = 0, cur = 0;
-  for (int k = 0; k < iters; ++k) {
-    const int pending = k > 0 ? 1 : 0;
-    if (fused) {
-      const int out = in ^ 1;
-      // every local band in ONE launch (BandDev table of this parity); the rows at
-      // the band edges land in the neighbours' halo rows / the send buffers
-      auto launch = [&](int mode, int grid) {
-        if (grid <= 0) return;
-        // (XCD-contiguous tile order like the un-split step: the band of a block is
-        // looked up after the remap, so a run may span bands)
-        const int xcd = xcd_opt == 0 ? 0 : (xcd_opt == 1 ? grid >= 64 : grid >= 2048);
-        BandArgs ba{sums_of(k - 1), nullptr, total, 0, mode, 0, 0, band_dev[in], nl, xcd};
-        hipLaunchKernelGGL((integrate_shared2d_kernel<true, true>), dim3(grid), dim3(kBlock), 0, st,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bs[0].p,
-                           nullptr, nullptr, cap0, nullptr, nullptr, pending ? 3 : 0, 0,
-                           bs[0].tiles.ntx, ba);
-      };
-      auto exchange_fused = [&](hipStream_t s_) -> int {
-        if (int rc = p2p(s_)) return rc;
-        launch_rows(after[out], s_);
-        SFM_LAUNCH_CHECK();
-        return SFM_OK;
-      };
-      sfm::prof_begin(sfm::kProfMesh, st);
-      if (overlap) {
-        launch(1, grid_mode[1]);
-        SFM_LAUNCH_CHECK();
-        SFM_HIP_CHECK(hipEventRecord(ev_edge, st));
-        SFM_HIP_CHECK(hipStreamWaitEvent(xs, ev_edge, 0));
-        join.forked = true;
-        if (int rc = exchange_fused(xs)) return rc;
-        launch(2, grid_mode[2]);
-        SFM_LAUNCH_CHECK();
-        sfm::prof_end(sfm::kProfMesh, st);
-        SFM_HIP_CHECK(hipEventRecord(ev_int, st));
-        SFM_HIP_CHECK(hipStreamWaitEvent(xs, ev_int, 0));
-        if (d0.fire)
-          if (int rc = gather_sums(k, xs)) return rc;
-        SFM_HIP_CHECK(hipEventRecord(ev_x, xs));
-        SFM_HIP_CHECK(hipStreamWaitEvent(st, ev_x, 0));
-        join.forked = false;
-      } else {
-        launch(0, grid_mode[0]);
-        SFM_LAUNCH_CHECK();
-        sfm::prof_end(sfm::kProfMesh, st);
-        if (int rc = exchange_fused(st)) return rc;
-        if (d0.fire)
-          if (int rc = gather_sums(k, st)) return rc;
-      }
-      in = out;
-      if (d0.fire) cur ^= 1;
-    } else {
-      // advance / integrate pair in place; the rows were exchanged after the
-      // previous integrate (or by `begin`)
-      for (int i = 0; i < nl; ++i) {
-        BandState& s = bs[i];
-        const SfmMeshDesc& d = b->bands[i];
-        if (s.p.ncomp == 2)
-          hipLaunchKernelGGL(advance_kernel<2>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.v, d.a,
-                             s.p, &s.w.scal[cur], &s.w.scal[cur ^ 1], sums_of(k - 1), total,
-                             pending, s.w.colsum);
-        else
-          hipLaunchKernelGGL(advance_kernel<3>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.v, d.a,
-                             s.p, &s.w.scal[cur], &s.w.scal[cur ^ 1], sums_of(k - 1), total,
-                             pending, s.w.colsum);
-        SFM_LAUNCH_CHECK();
-      }
-      cur ^= 1;
-      sfm::prof_begin(sfm::kProfMesh, st);
-      for (int i = 0; i < nl; ++i) {
-        BandState& s = bs[i];
-        const SfmMeshDesc& d = b->bands[i];
-        if (s.p.ncomp == 2)
-          hipLaunchKernelGGL(integrate_kernel<2>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.v, d.a,
-                             d.prev, s.p, &s.w.scal[cur], cap0, s.w.partials);
-        else
-          hipLaunchKernelGGL(integrate_kernel<3>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.v, d.a,
-                             d.prev, s.p, &s.w.scal[cur], cap0, s.w.partials);
-        SFM_LAUNCH_CHECK();
-        if (s.p.fire) {
-          hipLaunchKernelGGL(shard_sums_kernel, dim3(1), dim3(kBlock), 0, st, s.w.partials,
-                             s.grid, sums_of(k) + (size_t)(b->rank * nl + i) * kNP);
-          SFM_LAUNCH_CHECK();
-        }
-      }
-      sfm::prof_end(sfm::kProfMesh, st);
-      if (int rc = exchange(0, st)) return rc;
-      if (d0.fire)
-        if (int rc = gather_sums(k, st)) return rc;
+  // -- begin: scalars, a = F(x) + pull on the local rows of every band --------
+  int begin(const SfmFireState& fire) {
+    if (overlap) {
+      SFM_HIP_CHECK(hipEventCreateWithFlags(&ev_edge, hipEventDisableTiming));
+      SFM_HIP_CHECK(hipEventCreateWithFlags(&ev_int, hipEventDisableTiming));
+      SFM_HIP_CHECK(hipEventCreateWithFlags(&ev_x, hipEventDisableTiming));
     }
+    s0 = initial_scalars(fire);
+    cap0 = fire.cap;
+    for (int i = 0; i < nl; ++i) {
+      BandState& s = bs[i];
+      const SfmMeshDesc& d = b->bands[i];
+      SFM_HIP_CHECK(hipMemcpyAsync(&s.w.scal[0], &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+      if (fused) {
+        SFM_HIP_CHECK(hipMemsetAsync(s.w.ticket, 0, 2 * sizeof(int), st));
+        SFM_HIP_CHECK(hipMemsetAsync(s.w.tile_part, 0, (size_t)s.tiles.tiles * kNP * sizeof(u64), st));
+      }
+      SFM_LAUNCH_NCOMP(force_kernel, s.p.ncomp, s.grid, kBlock, st, d.x, d.prev, d.a, s.p, cap0,
+                       s.p.has_prev);
+    }
+    // the halo rows' a (and, from the second chunk on, nothing else) is stale
+    return on_comm_stream([&](hipStream_t s_) { return exchange(0, s_); });
   }
-  const float* sums_last = sums_of(iters - 1);
+
+  // -- the loop -----------------------------------------------------------------
+  // Every local band in ONE launch (BandDev table of this parity); the rows at
+  // the band edges land in the neighbours' halo rows / the send buffers.
+  // (XCD-contiguous tile order like the un-split step: the band of a block is
+  // looked up after the remap, so a run may span bands)
+  int launch_fused(int k, int mode) {
+    const int grid = grid_mode[mode];
+    if (grid <= 0) return SFM_OK;
+    BandArgs ba{sums_of(k - 1), nullptr, total, 0, mode, 0, 0, band_dev[in], nl,
+                xcd_order(xcd_tri, grid)};
+    hipLaunchKernelGGL((integrate_shared2d_kernel<true, true>), dim3(grid), dim3(kBlock), 0, st,
+                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bs[0].p,
+                       nullptr, nullptr, cap0, nullptr, nullptr, k > 0 ? 3 : 0, 0,
+                       bs[0].tiles.ntx, ba);
+    SFM_LAUNCH_CHECK();
+    return SFM_OK;
+  }
+  int step_fused(int k) {
+    const int out = in ^ 1;
+    sfm::prof_begin(sfm::kProfMesh, st);
+    if (overlap) {
+      if (int rc = launch_fused(k, 1)) return rc;
+      SFM_HIP_CHECK(hipEventRecord(ev_edge, st));
+      SFM_HIP_CHECK(hipStreamWaitEvent(xs, ev_edge, 0));
+      join.forked = true;
+      if (int rc = exchange_after(out, xs)) return rc;
+      if (int rc = launch_fused(k, 2)) return rc;
+      sfm::prof_end(sfm::kProfMesh, st);
+      SFM_HIP_CHECK(hipEventRecord(ev_int, st));
+      SFM_HIP_CHECK(hipStreamWaitEvent(xs, ev_int, 0));
+      if (int rc = gather_sums(k, xs)) return rc;
+      SFM_HIP_CHECK(hipEventRecord(ev_x, xs));
+      SFM_HIP_CHECK(hipStreamWaitEvent(st, ev_x, 0));
+      join.forked = false;
+    } else {
+      if (int rc = launch_fused(k, 0)) return rc;
+      sfm::prof_end(sfm::kProfMesh, st);
+      if (int rc = exchange_after(out, st)) return rc;
+      if (int rc = gather_sums(k, st)) return rc;
+    }
+    in = out;
+    if (d0.fire) cur ^= 1;
+    return SFM_OK;
+  }
+  // advance / integrate pair in place; the rows were exchanged after the
+  // previous integrate (or by `begin`)
+  int step_pair(int k) {
+    for (int i = 0; i < nl; ++i) {
+      BandState& s = bs[i];
+      const SfmMeshDesc& d = b->bands[i];
+      SFM_LAUNCH_NCOMP(advance_kernel, s.p.ncomp, s.grid, kBlock, st, d.x, d.v, d.a, s.p,
+                       &s.w.scal[cur], &s.w.scal[cur ^ 1], sums_of(k - 1), total, k > 0 ? 1 : 0,
+                       s.w.colsum);
+    }
+    cur ^= 1;
+    sfm::prof_begin(sfm::kProfMesh, st);
+    for (int i = 0; i < nl; ++i) {
+      BandState& s = bs[i];
+      const SfmMeshDesc& d = b->bands[i];
+      SFM_LAUNCH_NCOMP(integrate_kernel, s.p.ncomp, s.grid, kBlock, st, d.x, d.v, d.a, d.prev,
+                       s.p, &s.w.scal[cur], cap0, s.w.partials);
+      if (s.p.fire) {
+        hipLaunchKernelGGL(shard_sums_kernel, dim3(1), dim3(kBlock), 0, st, s.w.partials,
+                           s.grid, sums_of(k) + (size_t)(b->rank * nl + i) * kNP);
+        SFM_LAUNCH_CHECK();
+      }
+    }
+    sfm::prof_end(sfm::kProfMesh, st);
+    if (int rc = exchange(0, st)) return rc;
+    return gather_sums(k, st);
+  }
 
   // -- finish: pending gate / drift of the last step, statistics ---------------
-  const Scalars* final_scal = nullptr;
-  for (int i = 0; i < nl; ++i) {
-    BandState& s = bs[i];
-    const SfmMeshDesc& d = b->bands[i];
-    if (in == 1) {
-      const size_t bytes = (size_t)s.p.ncomp * s.p.N * sizeof(float);
-      for (int k = 0; k < 3; ++k)
-        SFM_HIP_CHECK(hipMemcpyAsync(s.set[0][k], s.set[1][k], bytes, hipMemcpyDeviceToDevice, st));
-    }
-    int mode = iters > 0 ? 1 : 0;
-    int c = cur;
-    if (fused && iters > 0 && s.p.fire) {
-      // same (band-order) reduction as the step kernels', then finish with the
-      // scalars as they are
-      hipLaunchKernelGGL(band_scalars_kernel, dim3(1), dim3(64), 0, st, &s.w.scal[c],
-                         &s.w.scal[c ^ 1], sums_last, total, s.p);
+  int finish(SfmFireState* fire, SfmChunkStats* stats) {
+    const float* sums_last = sums_of(iters - 1);
+    const Scalars* final_scal = nullptr;
+    for (int i = 0; i < nl; ++i) {
+      BandState& s = bs[i];
+      const SfmMeshDesc& d = b->bands[i];
+      if (in == 1) {
+        const size_t bytes = (size_t)s.p.ncomp * s.p.N * sizeof(float);
+        for (int k = 0; k < 3; ++k)
+          SFM_HIP_CHECK(hipMemcpyAsync(s.set[0][k], s.set[1][k], bytes, hipMemcpyDeviceToDevice, st));
+      }
+      int mode = iters > 0 ? 1 : 0;
+      int c = cur;
+      if (fused && iters > 0 && s.p.fire) {
+        // same (band-order) reduction as the step kernels', then finish with the
+        // scalars as they are
+        hipLaunchKernelGGL(band_scalars_kernel, dim3(1), dim3(64), 0, st, &s.w.scal[c],
+                           &s.w.scal[c ^ 1], sums_last, total, s.p);
+        SFM_LAUNCH_CHECK();
+        c ^= 1;
+        mode = 2;
+      }
+      SFM_LAUNCH_NCOMP(finish_kernel, s.p.ncomp, s.grid, kBlock, st, d.x, d.v, s.p, &s.w.scal[c],
+                       &s.w.scal[c ^ 1], sums_last, total, mode, s.w.stat_part, s.w.colsum);
+      hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, s.w.stat_part, s.grid,
+                         stats_all + (size_t)(b->rank * nl + i) * 2);
       SFM_LAUNCH_CHECK();
-      c ^= 1;
-      mode = 2;
+      // scal[c ^ 1]: the chunk's final scalars (identical in every band)
+      if (i == 0) final_scal = &s.w.scal[c ^ 1];
     }
-    if (s.p.ncomp == 2)
-      hipLaunchKernelGGL(finish_kernel<2>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.v, s.p,
-                         &s.w.scal[c], &s.w.scal[c ^ 1], sums_last, total, mode, s.w.stat_part,
-                         s.w.colsum);
-    else
-      hipLaunchKernelGGL(finish_kernel<3>, dim3(s.grid), dim3(kBlock), 0, st, d.x, d.v, s.p,
-                         &s.w.scal[c], &s.w.scal[c ^ 1], sums_last, total, mode, s.w.stat_part,
-                         s.w.colsum);
-    SFM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(stats_kernel, dim3(1), dim3(kBlock), 0, st, s.w.stat_part, s.grid,
-                       stats_all + (size_t)(b->rank * nl + i) * 2);
-    SFM_LAUNCH_CHECK();
-    // scal[c ^ 1]: the chunk's final scalars (identical in every band)
-    if (i == 0) final_scal = &s.w.scal[c ^ 1];
+    if (n_ranks > 1)
+      if (int rc = on_comm_stream([&](hipStream_t s_) {
+            return allgather(stats_all, (size_t)nl * 2, s_);
+          }))
+        return rc;
+    Scalars s1;
+    float hs[2 * kMaxBlocks];
+    if (int rc = fetch_results(st, final_scal, &s1, stats_all, hs, (size_t)2 * total)) return rc;
+    if (d0.fire) carry_fire(s1, fire);
+    float ek = 0.f, vm = 0.f;
+    for (int g = 0; g < total; ++g) {   // band order, float32 like the device sums
+      ek = ek + hs[2 * g];
+      vm = std::max(vm, hs[2 * g + 1]);
+    }
+    stats->e_kin = ek;
+    stats->v_max = vm;
+    return SFM_OK;
   }
-  if (n_ranks > 1)
-    if (int rc = on_comm_stream([&](hipStream_t s_) {
-          return allgather(stats_all, (size_t)nl * 2, s_);
-        }))
-      return rc;
-  Scalars s1;
-  float hs[2 * kMaxBlocks];
-  SFM_HIP_CHECK(hipMemcpyAsync(&s1, final_scal, sizeof(s1), hipMemcpyDeviceToHost, st));
-  SFM_HIP_CHECK(hipMemcpyAsync(hs, stats_all, sizeof(float) * 2 * total, hipMemcpyDeviceToHost, st));
-  SFM_HIP_CHECK(hipStreamSynchronize(st));
-  if (d0.fire) {
-    fire->dt = s1.dt;
-    fire->alpha = s1.alpha;
-    fire->n_pos = s1.n_pos;
-    fire->cap = s1.cap;
-  }
-  float ek = 0.f, vm = 0.f;
-  for (int g = 0; g < total; ++g) {   // band order, float32 like the device sums
-    ek = ek + hs[2 * g];
-    vm = std::max(vm, hs[2 * g + 1]);
-  }
-  stats->e_kin = ek;
-  stats->v_max = vm;
-  return SFM_OK;
+};
+
+}  // namespace
+
+extern "C" {
+
+size_t sfm_mesh_banded_scratch_bytes(const SfmBandedDesc* b) {
+  if (!b || !b->bands || b->n_local < 1) return 0;
+  const SfmMeshDesc& d = b->bands[0];
+  const size_t row = 3 * (size_t)d.ncomp * d.shape[0] * d.shape[1] * d.shape[3];
+  sfm::Carver c(nullptr);
+  const size_t total = (size_t)std::max(b->n_ranks, 1) * b->n_local;
+  c.take<float>(2 * total * kNP);      // sums of all bands, double buffered by step parity
+  c.take<float>(total * 2);            // e_kin, v_max of all bands
+  c.take<BandDev>(2 * (size_t)b->n_local);  // multi-band launch tables (two parities)
+  for (int i = 0; i < b->n_local; ++i)
+    for (int k = 0; k < 4; ++k) c.take<float>(row);
+  return c.total();
 }
+
+int sfm_mesh_relax_banded(const SfmBandedDesc* b, SfmFireState* fire, SfmChunkStats* stats) {
+  if (!b || !b->bands || !b->shards || !fire || !stats)
+    return sfm::fail(SFM_ERR_INVALID, "banded: NULL argument");
+  if (b->n_local < 1 || b->n_local > kMaxLocalBands)
+    return sfm::fail(SFM_ERR_INVALID, "banded: 1..%d bands per rank", kMaxLocalBands);
+  BandedRun run(b);
+  if (int rc = run.validate()) return rc;
+  if (int rc = run.setup_bands()) return rc;
+  run.build_jobs(0);
+  if (run.fused) {
+    run.build_jobs(1);
+    if (int rc = run.upload_tables()) return rc;
+  }
+  if (int rc = run.begin(*fire)) return rc;
+  for (int k = 0; k < run.iters; ++k)
+    if (int rc = run.fused ? run.step_fused(k) : run.step_pair(k)) return rc;
+  return run.finish(fire, stats);
+}
+
+#undef SFM_LAUNCH_NCOMP
 
 }  // extern "C"

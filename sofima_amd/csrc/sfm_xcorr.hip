@@ -1367,8 +1367,7 @@ int group_rows(const SfmXcorrDesc* d) {
 constexpr int kMaskedGroups = 8;
 
 int masked_groups() {
-  const char* e = sfm::option("SFM_MASKED_GROUPS");
-  const int n = e ? std::atoi(e) : kMaskedGroups;
+  const int n = sfm::option_int("SFM_MASKED_GROUPS", kMaskedGroups);
   return n < 1 ? 1 : n;
 }
 
@@ -1413,14 +1412,12 @@ int surface_one(const SfmXcorrDesc* d, const Geo& g, float* surface) {
 
 // SFM_MASKED_DEADROWS=0: the peak sweeps of the masked path read every row.
 bool live_rows_enabled() {
-  const char* e = sfm::option("SFM_MASKED_DEADROWS");
-  return !(e && e[0] == '0');
+  return sfm::option_on("SFM_MASKED_DEADROWS");
 }
 
 // SFM_MASKED_BLKMAX=0: the peak sweep of the masked path reads every live row.
 bool blkmax_enabled() {
-  const char* e = sfm::option("SFM_MASKED_BLKMAX");
-  return !(e && e[0] == '0');
+  return sfm::option_on("SFM_MASKED_BLKMAX");
 }
 
 int peaks_one(const SfmXcorrDesc* d, const Geo& g, float* peaks) {

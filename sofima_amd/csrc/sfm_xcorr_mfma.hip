@@ -4523,14 +4523,12 @@ constexpr Variant kVariants[] = {{3, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}, {8, 9},
                                  {15, 11}, {20, 11}};
 
 bool exact_enabled() {
-  const char* e = sfm::measure_option("SFM_MFMA_EXACT");
-  return !(e && e[0] == '0');
+  return sfm::measure_option_on("SFM_MFMA_EXACT");
 }
 
 // SFM_MFMA_PRUNE=0: every dy tile is computed (tests, measurements).
 bool prune_enabled() {
-  const char* e = sfm::option("SFM_MFMA_PRUNE");
-  return !(e && e[0] == '0');
+  return sfm::option_on("SFM_MFMA_PRUNE");
 }
 
 int pick_variant(int px, int qx) {
@@ -4620,8 +4618,6 @@ Ws carve_ws(const SfmXcorrDesc* d, void* base) {
   return w;
 }
 
-int device_cus();
-
 template <int NCA, int NCE, int MODE>
 int launch_one(const MfmaArgs& a, int grid, size_t lds, hipStream_t st) {
   // (search-window variants: eight waves per workgroup, see WIDE8 in the kernel)
@@ -4649,17 +4645,17 @@ int launch_one(const MfmaArgs& a, int grid, size_t lds, hipStream_t st) {
   int wg_per_cu = per_cu;
   {
     // (a measurement switch; read per call so that a test can flip it)
-    const char* cap = sfm::measure_option("SFM_MFMA_MAX_WG_PER_CU");
-    if (cap && std::atoi(cap) > 0) wg_per_cu = std::min(wg_per_cu, std::atoi(cap));
+    const int cap = sfm::measure_option_int("SFM_MFMA_MAX_WG_PER_CU", 0);
+    if (cap > 0) wg_per_cu = std::min(wg_per_cu, cap);
   }
-  grid = std::min(grid, device_cus() * wg_per_cu);
+  grid = std::min(grid, sfm::device_cus() * wg_per_cu);
   {
     // SFM_MFMA_GRID=n (tests): at most n workgroups, so that a small batch runs
     // MANY patches through one workgroup -- the state a workgroup carries from
     // patch to patch (previous need mask / hot columns / seed block, the probe's
     // self-switch-off) is otherwise only exercised by full-size fields.
-    const char* g = sfm::option("SFM_MFMA_GRID");
-    if (g && std::atoi(g) > 0) grid = std::min(grid, std::atoi(g));
+    const int g = sfm::option_int("SFM_MFMA_GRID", 0);
+    if (g > 0) grid = std::min(grid, g);
   }
   sfm::prof_begin(sfm::kProfXcorr, st);
   hipLaunchKernelGGL((xcorr_mfma_kernel<NCA, NCE, MODE>), dim3(grid),
@@ -4704,15 +4700,6 @@ int launch_mode(int vi, const MfmaArgs& a, int mode, int grid, size_t lds,
     case 8: return launch_variant<20, 11>(a, mode, grid, lds, st);
   }
   return sfm::fail(SFM_ERR_INVALID, "no MFMA variant");
-}
-
-int device_cus() {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-  }
-  return cus;
 }
 
 // Geometry, image pointers, LDS layout and the static tile schedule shared by
@@ -4798,8 +4785,7 @@ const int kMaskedPasses[8][2] = {
 
 // SFM_MASKED_FAST=0 (tests): every patch takes all eight passes.
 bool masked_all_passes() {
-  const char* e = sfm::option("SFM_MASKED_FAST");
-  return e && e[0] == '0';
+  return !sfm::option_on("SFM_MASKED_FAST");
 }
 
 struct MaskedWs {
@@ -4907,11 +4893,9 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
   a.aux_n = w.aux_n;
   a.surface = surface;
   {
-    const char* e = sfm::measure_option("SFM_MFMA_QUEUE");
-    a.work_counter = (e && e[0] == '0') ? nullptr : w.counter;
+    a.work_counter = sfm::measure_option_on("SFM_MFMA_QUEUE") ? w.counter : nullptr;
     a.clk = reinterpret_cast<long long*>(w.counter + 16);
-    const char* p = sfm::measure_option("SFM_MFMA_PRIO");
-    a.prio_mode = p ? std::atoi(p) : 0;
+    a.prio_mode = sfm::measure_option_int("SFM_MFMA_PRIO", 0);
   }
   if (fp) {
     a.do_peaks = 1;
@@ -4941,20 +4925,14 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
     a.prune_k[1] = col_skip_hi(a.nq);
     a.prune_k[2] = col_skip_2(a.nq);
     a.prune_k[3] = col_skip_3(a.nq);
-    {
-      const char* e = sfm::measure_option("SFM_MFMA_PROBE");  // "0": no seed probe
-      a.probe = !(e && e[0] == '0');
-    }
+    a.probe = sfm::measure_option_on("SFM_MFMA_PROBE");  // "0": no seed probe
     a.count_tiles = sfm::profiling() ? 1 : 0;
     {
       // least number of row groups between two tests inside the row loop of the
       // lazy modes ("0": no tests); each test schedules the next, see check_after
-      const char* e = sfm::option("SFM_MFMA_EARLY");
-      a.early = e ? std::atoi(e) : 1;
-      const char* ta = sfm::measure_option("SFM_MFMA_TOUCH_ALL");
-      a.touch_all = ta && ta[0] == '1';
-      const char* nw = sfm::option("SFM_MFMA_NARROW");
-      a.narrow = nw ? std::atoi(nw) : 64;   // widest narrowing allowed (0: off)
+      a.early = sfm::option_int("SFM_MFMA_EARLY", 1);
+      a.touch_all = sfm::measure_option_tri("SFM_MFMA_TOUCH_ALL") == 1;
+      a.narrow = sfm::option_int("SFM_MFMA_NARROW", 64);   // widest narrowing allowed (0: off)
       if (a.early < 0 || a.P[0] > kEarlyRows) a.early = 0;
     }
     a.prune = same && prune_enabled() && a.n_order <= kBoundTiles &&
@@ -4967,19 +4945,13 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
   // lazy surface stores: the flow path only (fused peak search: nobody else
   // reads the surface), tile masks of 31 bits, SFM_MFMA_LAZY=0 switches it off
   bool lazy = same && fp != nullptr && a.n_order <= 31 && a.skipmask != nullptr;
-  {
-    const char* e = sfm::option("SFM_MFMA_LAZY");
-    if (e && e[0] == '0') lazy = false;
-  }
+  if (!sfm::option_on("SFM_MFMA_LAZY")) lazy = false;
   // The correction table built in the epilogue of the tiles that are stored instead
   // of by the prep kernel (kModeSameExactLazyG): pays where few tiles reach an
   // epilogue, i.e. with the pruning on (the un-pruned launch, every tile finished,
   // keeps the table).  SFM_MFMA_LAZYG=0: off.
-  {
-    const char* e = sfm::option("SFM_MFMA_LAZYG");
-    a.lazy_g = exact && lazy && a.prune && !(e && e[0] == '0') && a.P[0] % 16 == 0 &&
-               a.P[0] <= 160 && a.P[1] <= 160 && a.P[0] >= 32;
-  }
+  a.lazy_g = exact && lazy && a.prune && sfm::option_on("SFM_MFMA_LAZYG") &&
+             a.P[0] % 16 == 0 && a.P[0] <= 160 && a.P[1] <= 160 && a.P[0] >= 32;
   // Region behind the patches: the four 1-D correction arrays, reused as the
   // arg-max scratch of the fused peak search, then the running-max word.
   size_t r_bytes = same ? (size_t)4 * w.aux_n * 4 : 0;
@@ -5105,19 +5077,12 @@ int mfma_i8_masked(const SfmXcorrDesc* d, void* ws_base, float* surface,
   }
   g.batch = d->batch;
   g.all_passes = masked_all_passes() ? 1 : 0;
-  {
-    const char* e = sfm::option("SFM_MASKED_DEADROWS");
-    g.dead_rows = !(e && e[0] == '0');
-  }
-  {
-    const char* e = sfm::option("SFM_PHASE_XCD");
-    g.xcd_map = !(e && e[0] == '0');
-  }
+  g.dead_rows = sfm::option_on("SFM_MASKED_DEADROWS");
+  g.xcd_map = sfm::option_on("SFM_PHASE_XCD");
   g.maxima = maxima;
   {
     // class 0 maxima from the axes (SFM_MASKED_AXISMAX=0: the sweep over all shifts)
-    const char* e = sfm::option("SFM_MASKED_AXISMAX");
-    g.axis_max = !(e && e[0] == '0') && a.P[0] == a.Q[0] && a.P[1] == a.Q[1] &&
+    g.axis_max = sfm::option_on("SFM_MASKED_AXISMAX") && a.P[0] == a.Q[0] && a.P[1] == a.Q[1] &&
                  a.P[0] <= kAxisMaxLen && a.P[1] <= kAxisMaxLen;
   }
   g.group = w.group;

@@ -142,6 +142,19 @@ def band_bounds(n_rows: int, n_bands: int) -> list[tuple[int, int]]:
   return list(zip(edges[:-1], edges[1:]))
 
 
+def _band_slices(n_rows: int, n_bands: int, rank: int, per_rank: int):
+  """(lo, hi, own0, own1) per local band of `rank`: rows [lo, hi) of the mesh --
+  the owned rows plus one halo row per existing neighbour -- of which the local
+  rows [own0, own1) are owned."""
+  bounds = band_bounds(n_rows, n_bands)
+  for i in range(per_rank):
+    g = rank * per_rank + i
+    y0, y1 = bounds[g]
+    lo = y0 - (1 if g > 0 else 0)
+    hi = y1 + (1 if g < n_bands - 1 else 0)
+    yield lo, hi, y0 - lo, y1 - lo
+
+
 class HipBand:
   """One band of a mesh on the current GPU, stepped through the C ABI
   (sfm_mesh_shard_*).  Local arrays are [C, ..., rows, X]: the owned rows plus
@@ -436,39 +449,24 @@ def relax_mesh_sharded(x, prev, config, mesh_force=None, group=None,
   rank, ws = world(group)
   x = np.asarray(x, dtype=np.float32)
   prev = None if prev is None else np.asarray(prev, dtype=np.float32)
-  if config.start_cap != config.final_cap:
-    if not config.fire:
-      raise NotImplementedError(
-          'Adaptive force capping is only supported with FIRE.')
-    if config.cap_scale <= 1:
-      raise ValueError(
-          'The scaling factor for the force cap has to be larger '
-          'than 1 when the initial and final cap are different.')
+  from . import mesh
+  mesh._check_cap_schedule(config)
   if config.remove_drift and x.ndim == 5:
     raise NotImplementedError('per-column drift removal is not sharded')
   spec = None
   if band_factory is None:
-    from . import mesh
     spec = mesh._resolve_force(mesh.inplane_force if mesh_force is None else mesh_force)
     band_factory = HipBand
   n_bands = ws * bands_per_rank
-  bounds = band_bounds(x.shape[-2], n_bands)
   global_nodes = int(np.prod(x.shape[1:]))
   bands = []
-  for i in range(bands_per_rank):
-    g = rank * bands_per_rank + i
-    y0, y1 = bounds[g]
-    lo = y0 - (1 if g > 0 else 0)
-    hi = y1 + (1 if g < n_bands - 1 else 0)
+  for lo, hi, own0, own1 in _band_slices(x.shape[-2], n_bands, rank, bands_per_rank):
     bands.append(band_factory(
         x[..., lo:hi, :], None if prev is None else prev[..., lo:hi, :], config,
-        spec, (y0 - lo, y1 - lo), global_nodes, n_bands))
+        spec, (own0, own1), global_nodes, n_bands))
   transport = transport or BandTransport(group)
 
-  t = 0
-  dt, alpha, cap = config.dt, config.alpha, config.start_cap
-  e_kin = []
-  while t < config.max_iters:
+  def run_chunk(dt, alpha, cap):
     for b in bands:
       b.begin(dt, alpha, cap)
     for k in range(config.num_iters):
@@ -482,19 +480,12 @@ def relax_mesh_sharded(x, prev, config, mesh_force=None, group=None,
     if config.fire and config.num_iters > 0:
       transport.gather_sums(bands)
     stats = transport.gather_stats([b.finish() for b in bands])
-    t += config.num_iters
     ek = np.float32(0)
     for s in stats:                      # fixed (global band) order
       ek = np.float32(ek + s[4])
-    e_kin.append(float(ek))
-    v_max = float(max(s[5] for s in stats))
-    if config.fire:
-      dt, alpha, _, cap = stats[0][:4]
-    if v_max < config.stop_v_max:
-      if np.float32(cap) >= np.float32(config.final_cap):
-        break
-      cap = min(cap * config.cap_scale, config.final_cap)
+    return (*stats[0][:4], float(ek), float(max(s[5] for s in stats)))
 
+  e_kin, t = mesh._relax_loop(config, run_chunk)
   owned = transport.gather_stats([b.owned_x() for b in bands])
   return np.concatenate(owned, axis=-2), e_kin, t
 
@@ -548,14 +539,7 @@ def relax_mesh_banded(x, prev, config, mesh_force=None, group=None,
   rank, ws = world(group)
   x = np.asarray(x, dtype=np.float32)
   prev = None if prev is None else np.asarray(prev, dtype=np.float32)
-  if config.start_cap != config.final_cap:
-    if not config.fire:
-      raise NotImplementedError(
-          'Adaptive force capping is only supported with FIRE.')
-    if config.cap_scale <= 1:
-      raise ValueError(
-          'The scaling factor for the force cap has to be larger '
-          'than 1 when the initial and final cap are different.')
+  mesh._check_cap_schedule(config)
   if config.remove_drift and x.ndim == 5:
     raise NotImplementedError('per-column drift removal is not sharded')
   spec = mesh._resolve_force(mesh.inplane_force if mesh_force is None else mesh_force)
@@ -581,18 +565,14 @@ def relax_mesh_banded(x, prev, config, mesh_force=None, group=None,
     comm = own_comm = RcclComm(group)
   n_local = int(bands_per_rank)
   n_bands = ws * n_local
-  bounds = band_bounds(x.shape[-2], n_bands)
   global_nodes = int(np.prod(x.shape[1:]))
 
   descs = (_abi.SfmMeshDesc * n_local)()
   shards = (_abi.SfmMeshShard * n_local)()
   keep = []
   owns = []
-  for i in range(n_local):
-    g = rank * n_local + i
-    y0, y1 = bounds[g]
-    lo = y0 - (1 if g > 0 else 0)
-    hi = y1 + (1 if g < n_bands - 1 else 0)
+  for i, (lo, hi, own0, own1) in enumerate(
+      _band_slices(x.shape[-2], n_bands, rank, n_local)):
     x_t = _dev.as_device_f32(x[..., lo:hi, :], dev, copy=True)
     v_t = torch.zeros_like(x_t)
     a_t = torch.empty_like(x_t)
@@ -600,10 +580,10 @@ def relax_mesh_banded(x, prev, config, mesh_force=None, group=None,
     probe = mesh._base_desc(x_t, spec, config.k, config.stride, config.prefer_orig_order)
     wsp = _dev.workspace(lib.sfm_mesh_workspace_bytes(C.byref(probe)), dev)
     descs[i] = mesh._chunk_desc(x_t, v_t, a_t, p_t, config, spec, wsp)
-    shards[i].own_y0, shards[i].own_y1 = y0 - lo, y1 - lo
+    shards[i].own_y0, shards[i].own_y1 = own0, own1
     shards[i].global_nodes = global_nodes
     keep.append((x_t, v_t, a_t, p_t, wsp))
-    owns.append((y0 - lo, y1 - lo))
+    owns.append((own0, own1))
 
   bd = _abi.SfmBandedDesc()
   bd.n_local = n_local
@@ -621,34 +601,27 @@ def relax_mesh_banded(x, prev, config, mesh_force=None, group=None,
   bd.scratch = scratch.data_ptr()
   bd.scratch_bytes = scratch.numel()
 
-  t = 0
-  dt, alpha, cap = config.dt, config.alpha, config.start_cap
-  e_kin = []
   spent = 0.0
+
+  def run_chunk(dt, alpha, cap):
+    nonlocal spent
+    fire = _abi.SfmFireState()
+    fire.dt, fire.alpha, fire.n_pos, fire.cap = (
+        np.float32(dt), np.float32(alpha), 0, np.float32(cap))
+    stats = _abi.SfmChunkStats()
+    for i in range(n_local):
+      descs[i].stream = _dev.stream_ptr()
+    t0 = time.perf_counter()
+    rc = lib.sfm_mesh_relax_banded(C.byref(bd), C.byref(fire), C.byref(stats))
+    if host is not None and host.error is not None:
+      raise host.error
+    _abi.check(rc)
+    spent += time.perf_counter() - t0
+    return (np.float32(fire.dt), np.float32(fire.alpha), int(fire.n_pos),
+            np.float32(fire.cap), float(stats.e_kin), float(stats.v_max))
+
   try:
-    while t < config.max_iters:
-      fire = _abi.SfmFireState()
-      fire.dt, fire.alpha, fire.n_pos, fire.cap = (
-          np.float32(dt), np.float32(alpha), 0, np.float32(cap))
-      stats = _abi.SfmChunkStats()
-      for i in range(n_local):
-        descs[i].stream = _dev.stream_ptr()
-      t0 = time.perf_counter()
-      rc = lib.sfm_mesh_relax_banded(C.byref(bd), C.byref(fire), C.byref(stats))
-      if host is not None and host.error is not None:
-        raise host.error
-      _abi.check(rc)
-      spent += time.perf_counter() - t0
-      t += config.num_iters
-      e_kin.append(float(stats.e_kin))
-      v_max = float(stats.v_max)
-      if config.fire:
-        dt, alpha, cap = (np.float32(fire.dt), np.float32(fire.alpha),
-                          np.float32(fire.cap))
-      if v_max < config.stop_v_max:
-        if np.float32(cap) >= np.float32(config.final_cap):
-          break
-        cap = min(cap * config.cap_scale, config.final_cap)
+    e_kin, t = mesh._relax_loop(config, run_chunk)
   finally:
     if own_comm is not None:
       torch.cuda.synchronize(dev)

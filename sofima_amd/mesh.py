@@ -457,18 +457,7 @@ def velocity_verlet(x, v, prev, config: IntegrationConfig, force_cap: float,
   return out
 
 
-def relax_mesh(x, prev, config: IntegrationConfig, mesh_force=inplane_force,
-               prev_fn=None) -> tuple[DeviceArray, list[float], int]:
-  """Simulates mesh relaxation (mesh.py:524-608).
-
-  Returns (relaxed positions [device], kinetic-energy history, steps run).
-  """
-  t = 0
-  dt = config.dt
-  alpha = config.alpha
-  e_kin = []
-  cap = config.start_cap
-
+def _check_cap_schedule(config: IntegrationConfig) -> None:
   if config.start_cap != config.final_cap:
     if not config.fire:
       raise NotImplementedError(
@@ -478,26 +467,24 @@ def relax_mesh(x, prev, config: IntegrationConfig, mesh_force=inplane_force,
           'The scaling factor for the force cap has to be larger '
           'than 1 when the initial and final cap are different.')
 
-  if prev is not None and prev_fn is not None:
-    raise ValueError('Only one of: "prev" and "prev_fn" can be specified.')
-  target, prev_call = _resolve_prev_fn(prev_fn)
 
-  spec = _resolve_force(mesh_force)
-  dev = _dev.device()
-  x_t = _dev.as_device_f32(x, dev, copy=True)
-  v_t = torch.zeros_like(x_t)
-  prev_t = None if prev is None else _dev.as_device_f32(prev, dev, copy=False)
+def _relax_loop(config: IntegrationConfig, run_chunk) -> tuple[list[float], int]:
+  """The chunk loop of relax_mesh (mesh.py:570-606): force-cap schedule, FIRE
+  carry-over, stopping.  `run_chunk(dt, alpha, cap)` runs `config.num_iters`
+  steps and returns (dt, alpha, n_pos, cap, e_kin, v_max).
 
+  Returns (kinetic-energy history, steps run).
+  """
+  t = 0
+  dt, alpha, cap = config.dt, config.alpha, config.start_cap
+  e_kin = []
   while t < config.max_iters:
-    _, fire, stats = _run_chunk(x_t, v_t, prev_t, config, cap, dt, alpha,
-                                spec, target, prev_call)
+    new_dt, new_alpha, n_pos, new_cap, e, v_max = run_chunk(dt, alpha, cap)
     t += config.num_iters
-    e_kin.append(float(stats.e_kin))
-    v_max = float(stats.v_max)
+    e_kin.append(float(e))
 
     if config.fire:
-      dt, alpha, n_pos, cap = (np.float32(fire.dt), np.float32(fire.alpha),
-                               int(fire.n_pos), np.float32(fire.cap))
+      dt, alpha, cap = new_dt, new_alpha, new_cap
       logging.info(
           't=%r: dt=%f, alpha=%f, n_pos=%d, cap=%f, v_max=%f, e_kin=%f',
           t, dt, alpha, n_pos, cap, v_max, e_kin[-1])
@@ -509,5 +496,31 @@ def relax_mesh(x, prev, config: IntegrationConfig, mesh_force=inplane_force,
         break
       # Increase cap to ensure progress towards the termination condition.
       cap = min(cap * config.cap_scale, config.final_cap)
+  return e_kin, t
 
+
+def relax_mesh(x, prev, config: IntegrationConfig, mesh_force=inplane_force,
+               prev_fn=None) -> tuple[DeviceArray, list[float], int]:
+  """Simulates mesh relaxation (mesh.py:524-608).
+
+  Returns (relaxed positions [device], kinetic-energy history, steps run).
+  """
+  _check_cap_schedule(config)
+  if prev is not None and prev_fn is not None:
+    raise ValueError('Only one of: "prev" and "prev_fn" can be specified.')
+  target, prev_call = _resolve_prev_fn(prev_fn)
+
+  spec = _resolve_force(mesh_force)
+  dev = _dev.device()
+  x_t = _dev.as_device_f32(x, dev, copy=True)
+  v_t = torch.zeros_like(x_t)
+  prev_t = None if prev is None else _dev.as_device_f32(prev, dev, copy=False)
+
+  def run_chunk(dt, alpha, cap):
+    _, fire, stats = _run_chunk(x_t, v_t, prev_t, config, cap, dt, alpha,
+                                spec, target, prev_call)
+    return (np.float32(fire.dt), np.float32(fire.alpha), int(fire.n_pos),
+            np.float32(fire.cap), float(stats.e_kin), float(stats.v_max))
+
+  e_kin, t = _relax_loop(config, run_chunk)
   return DeviceArray(x_t), e_kin, t

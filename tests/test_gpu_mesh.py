@@ -954,3 +954,51 @@ def test_forces_3d_with_nan_and_inf_positions_vs_oracle(gpu, shape):
     b = run()
   for u, w in zip(a, b):
     np.testing.assert_array_equal(u, w)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('shape,env', [
+    ((2, 1, 8, 8), {}),                                # one workgroup: small
+    ((2, 1, 20, 70), {}),                              # tiled, packed last column
+    ((2, 1, 20, 70), {'SFM_MESH_TILED': '0'}),
+    ((2, 2, 33, 62), {'SFM_MESH_PERSISTENT': '0'}),    # tiled step, multi-launch
+    ((3, 6, 7, 9), {}),                                # per-node 3-D
+])
+def test_chunk_plan_and_workspace_agree(gpu, shape, env):
+  """sfm_mesh_relax_chunk runs in exactly sfm_mesh_workspace_bytes and refuses
+  256 bytes less: both take their sizes from the same plan."""
+  import ctypes as C
+  import torch
+  from sofima_amd import _abi, mesh
+  lib = _abi.load()
+  rng = np.random.default_rng(3)
+  force = mesh.inplane_force if shape[0] == 2 else mesh.elastic_mesh_3d
+  cfg = mesh.IntegrationConfig(dt=0.001, gamma=0.0, k0=0.01, k=0.1,
+                               stride=(10,) * shape[0], num_iters=3, max_iters=3,
+                               stop_v_max=1e-9)
+  spec = mesh._resolve_force(force)
+  x0 = torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(gpu)
+  prev_t = torch.zeros_like(x0)
+
+  def run():
+    x_t, v_t, a_t = x0.clone(), torch.zeros_like(x0), torch.empty_like(x0)
+    probe = mesh._base_desc(x_t, spec, cfg.k, cfg.stride, cfg.prefer_orig_order)
+    need = lib.sfm_mesh_workspace_bytes(C.byref(probe))
+    assert need > 256 and need % 256 == 0
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu)
+    d = mesh._chunk_desc(x_t, v_t, a_t, prev_t, cfg, spec, ws)
+    fire = _abi.SfmFireState()
+    fire.dt, fire.alpha, fire.n_pos, fire.cap = cfg.dt, cfg.alpha, 0, cfg.start_cap
+    stats = _abi.SfmChunkStats()
+    d.workspace_bytes = need - 256
+    assert lib.sfm_mesh_relax_chunk(C.byref(d), C.byref(fire), C.byref(stats)) == -3
+    assert b'workspace needs %d bytes' % need in lib.sfm_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(x_t, x0)              # SFM_ERR_WORKSPACE: nothing ran
+    d.workspace_bytes = need
+    assert lib.sfm_mesh_relax_chunk(C.byref(d), C.byref(fire), C.byref(stats)) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(x_t).all() and not torch.equal(x_t, x0)
+    assert np.isfinite(stats.e_kin) and stats.v_max > 0
+
+  _with_env(env, run)

@@ -210,3 +210,116 @@ def test_flow_map3d_overlap_alignment_matches_reference_offsets(golden):
       grid = [(n - (p - st)) // st + p // 2 // st * 2 - 1
               for n, p, st in zip(size[::-1], patch, stride)]
       assert tuple(g[f'{name}_{i}'].shape[1:]) == tuple(grid)
+
+
+def _loop_config(**kw):
+  base = dict(dt=0.01, gamma=0.0, k0=0.1, k=0.1, stride=(10, 10), num_iters=10,
+              max_iters=100, stop_v_max=0.5)
+  base.update(kw)
+  return mesh.IntegrationConfig(**base)
+
+
+def _scripted(v_maxes, record, fire_out=None):
+  """run_chunk that plays back `v_maxes`; FIRE scalars: the chunk index as dt and
+  alpha, the cap it was given as float32 (like the kernel's) unless `fire_out`."""
+  def run_chunk(dt, alpha, cap):
+    i = len(record)
+    record.append((dt, alpha, cap))
+    out = fire_out or (np.float32(i + 1), np.float32(-(i + 1)), i, np.float32(cap))
+    return (*out, 100.0 + i, v_maxes[min(i, len(v_maxes) - 1)])
+  return run_chunk
+
+
+def test_relax_loop_fixed_cap_stops_at_first_slow_chunk():
+  calls = []
+  e_kin, steps = mesh._relax_loop(_loop_config(),
+                                  _scripted([3.0, 0.5, 0.49, 0.1], calls))
+  assert steps == 30 and len(calls) == 3      # 0.5 is not < stop_v_max
+  assert e_kin == [100.0, 101.0, 102.0]
+  # FIRE: dt / alpha of a chunk are what the previous one returned
+  assert calls[0][:2] == (0.01, 0.1)
+  assert calls[1][:2] == (np.float32(1), np.float32(-1))
+  assert calls[2][:2] == (np.float32(2), np.float32(-2))
+  assert all(c[2] == np.float32(1e6) for c in calls)
+
+
+def test_relax_loop_cap_schedule_stops_on_float32_final_cap():
+  calls = []
+  cfg = _loop_config(start_cap=0.1, final_cap=0.7, cap_scale=2)
+  e_kin, steps = mesh._relax_loop(cfg, _scripted([0.0], calls))
+  caps = [c[2] for c in calls]
+  np.testing.assert_array_equal(np.float32(caps), np.float32([0.1, 0.2, 0.4, 0.7]))
+  assert caps[3] == 0.7                      # min(0.8, final_cap): the Python float
+  assert float(np.float32(0.7)) < 0.7        # ... which the float32 cap reaches only as float32
+  assert steps == 40 and len(e_kin) == 4
+
+  # a chunk that hands back a cap below final_cap does not stop the loop
+  calls = []
+  below = np.nextafter(np.float32(0.7), np.float32(0))
+  _, steps = mesh._relax_loop(
+      cfg, _scripted([0.0], calls, fire_out=(np.float32(1), np.float32(1), 0, below)))
+  assert steps == 100 and len(calls) == 10
+
+
+def test_relax_loop_runs_to_max_iters_in_whole_chunks():
+  calls = []
+  cfg = _loop_config(num_iters=30, max_iters=100)
+  e_kin, steps = mesh._relax_loop(cfg, _scripted([9.0], calls))
+  assert steps == 120 and len(e_kin) == 4 and len(calls) == 4
+
+
+def test_relax_loop_without_fire_carries_nothing_over():
+  calls = []
+  cfg = _loop_config(fire=False, max_iters=30)
+  mesh._relax_loop(cfg, _scripted([9.0], calls))
+  assert calls == [(cfg.dt, cfg.alpha, cfg.start_cap)] * 3
+
+
+def test_check_cap_schedule_errors():
+  base = dict(dt=0.01, gamma=0.0, k0=0.1, k=0.1, stride=(10, 10), num_iters=5,
+              max_iters=10, stop_v_max=0.001)
+  with pytest.raises(NotImplementedError, match='only supported with FIRE'):
+    mesh._check_cap_schedule(mesh.IntegrationConfig(
+        fire=False, start_cap=1.0, final_cap=2.0, **base))
+  with pytest.raises(ValueError, match='has to be larger than 1'):
+    mesh._check_cap_schedule(mesh.IntegrationConfig(
+        start_cap=1.0, final_cap=2.0, cap_scale=1.0, **base))
+  mesh._check_cap_schedule(mesh.IntegrationConfig(**base))
+  mesh._check_cap_schedule(mesh.IntegrationConfig(
+      fire=False, start_cap=2.0, final_cap=2.0, cap_scale=1.0, **base))
+
+
+@pytest.mark.parametrize('n_rows', [5, 16, 33])
+@pytest.mark.parametrize('ranks,per_rank', [(1, 1), (1, 2), (2, 1), (1, 5), (5, 1)])
+def test_band_slices_tile_the_rows(n_rows, ranks, per_rank):
+  from sofima_amd import dist
+  n_bands = ranks * per_rank
+  bounds = dist.band_bounds(n_rows, n_bands)
+  owned = []
+  for rank in range(ranks):
+    got = list(dist._band_slices(n_rows, n_bands, rank, per_rank))
+    assert len(got) == per_rank
+    for i, (lo, hi, own0, own1) in enumerate(got):
+      g = rank * per_rank + i
+      # what the two drivers computed inline
+      y0, y1 = bounds[g]
+      want_lo = y0 - (1 if g > 0 else 0)
+      want_hi = y1 + (1 if g < n_bands - 1 else 0)
+      assert (lo, hi, own0, own1) == (want_lo, want_hi, y0 - want_lo, y1 - want_lo)
+      # one halo row per existing neighbour
+      assert own0 == (1 if g > 0 else 0)
+      assert hi - lo - own1 == (1 if g < n_bands - 1 else 0)
+      assert 0 <= lo and hi <= n_rows and own0 < own1
+      owned.append((lo + own0, lo + own1))
+  assert owned[0][0] == 0 and owned[-1][1] == n_rows
+  assert all(a[1] == b[0] for a, b in zip(owned[:-1], owned[1:]))
+
+
+def test_band_slices_expected_tuples():
+  from sofima_amd import dist
+  # 16 rows, 5 bands: owned [0,3) [3,6) [6,9) [9,12) [12,16)
+  assert [list(dist._band_slices(16, 5, r, 1)) for r in range(5)] == [
+      [(0, 4, 0, 3)], [(2, 7, 1, 4)], [(5, 10, 1, 4)], [(8, 13, 1, 4)],
+      [(11, 16, 1, 5)]]
+  assert list(dist._band_slices(16, 5, 0, 5)) == [
+      (0, 4, 0, 3), (2, 7, 1, 4), (5, 10, 1, 4), (8, 13, 1, 4), (11, 16, 1, 5)]
