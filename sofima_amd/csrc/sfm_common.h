@@ -65,6 +65,23 @@ inline int measure_option_int(const char* name, int dflt) {
 // 256 when the query fails.
 int device_cus();
 
+// "This kernel needs `bytes` of dynamic LDS": above the 48 KB every kernel may use
+// the kernel's limit on the current device is raised to it.  The limit only ever
+// rises (a launch that needs less is content with more), so the runtime is asked
+// once per device, kernel and new maximum, under the lock of the per-kernel table in
+// sfm_core.hip (g_kernels).
+int raise_lds_limit(const void* kernel, size_t bytes);
+template <typename K>
+int set_lds(K kernel, size_t bytes) {
+  return raise_lds_limit(reinterpret_cast<const void*>(kernel), bytes);
+}
+
+// Workgroups of `threads` threads and `lds` bytes of dynamic LDS that one CU of the
+// current device holds of `kernel` (the occupancy query, asked once per device,
+// kernel and LDS size, kept in the same table); 0 when the query fails.  A kernel is
+// always launched with one block size, so `threads` is not part of the key.
+int blocks_per_cu(const void* kernel, int threads, size_t lds);
+
 // FIRE scalars as the mesh kernels keep them on the device (sfm_mesh.hip) and
 // the pending per-step corrections derived from the previous step's sums.
 struct MeshScalars {

@@ -8,6 +8,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace sfm {
@@ -66,6 +67,46 @@ int device_cus() {
     if (cus <= 0) cus = 256;
   }
   return cus;
+}
+
+namespace {
+// What the launch layer knows of a kernel on a device (by device ordinal and kernel).
+struct KernelState {
+  size_t lds_limit = 0;            // dynamic-LDS limit raised so far (0: the default)
+  std::map<size_t, int> blocks;    // workgroups per CU by dynamic LDS bytes
+};
+std::mutex g_kernel_mu;
+std::map<std::pair<int, const void*>, KernelState> g_kernels;
+}  // namespace
+
+int raise_lds_limit(const void* kernel, size_t bytes) {
+  if (bytes <= 48 * 1024) return SFM_OK;
+  int dev = 0;
+  SFM_HIP_CHECK(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lk(g_kernel_mu);
+  KernelState& k = g_kernels[{dev, kernel}];
+  if (bytes > k.lds_limit) {
+    SFM_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      static_cast<int>(bytes)));
+    k.lds_limit = bytes;
+  }
+  return SFM_OK;
+}
+
+int blocks_per_cu(const void* kernel, int threads, size_t lds) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  std::lock_guard<std::mutex> lk(g_kernel_mu);
+  KernelState& k = g_kernels[{dev, kernel}];
+  auto it = k.blocks.find(lds);
+  if (it == k.blocks.end()) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, lds) != hipSuccess ||
+        n < 1)
+      n = 0;
+    it = k.blocks.emplace(lds, n).first;
+  }
+  return it->second;
 }
 
 namespace {

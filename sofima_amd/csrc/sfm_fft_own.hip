@@ -510,15 +510,6 @@ int pick_kt(int n) {
   return lds_bytes(n, 16) <= kLdsLimit ? 16 : lds_bytes(n, 8) <= kLdsLimit ? 8 : 4;
 }
 
-template <typename K>
-int set_lds(K kernel, size_t bytes) {
-  if (bytes > 48 * 1024)
-    SFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(bytes)));
-  return SFM_OK;
-}
-
 // Launchers that pick the KT instantiation.
 int launch_pencil(bool inv, const PencilArgs& a, long long tiles_outer, hipStream_t st) {
   const int kt = pick_kt(a.plan.N);

@@ -58,60 +58,28 @@
 //    operand planes (value, validity, split square); eight passes + an f64
 //    assembly kernel give Padfield's normalised correlation.
 //
+// 6. Search-window geometry (pre patch 161 .. 320 wide against a post patch of up to
+//    160): one workgroup of eight waves per CU, a tile job is one column half of a
+//    row tile (see the kernel).
+//
 // LDS per workgroup (P = Q = 160): pre patch (Py + 34) x 176 B + post patch
 // (Qy + 3) x 208 B = 68 KB -> two workgroups (8 waves) per CU.  Row pitches
 // 176 / 208 keep the b128 / b32 fragment reads bank-conflict free.
 //
-// Build switches (experiments): SFM_MFMA_TIMING
-// (in-kernel phase ticks), SFM_ABLATE_EPILOGUE, SFM_ABLATE_STORE, SFM_NO_TOUCH, SFM_AF_PREFETCH,
-// SFM_EPI_QG / SFM_EPI_DEPTH.
+// The row loop exists in three forms: A chunk outermost with in-place prefetch
+// (every mode but the general one), the column-half loop of the search-window
+// variants, and the plain B-outer loop of the general mode with up to ten chunks.
+// The waves of a workgroup draw dy tiles from a shared longest-first list through
+// an LDS counter: the four SIMDs do not run at the same speed (each shares its
+// matrix pipe with a wave of the other workgroup of the CU), and a static deal
+// spent ~17 % of a workgroup's time waiting for its slowest wave.
+//
+// Build switches (measurement builds): SFM_MFMA_TIMING
+// (in-kernel phase ticks), SFM_ABLATE_EPILOGUE, SFM_DEV_ONLY_WIDE.
 #include "sfm_common.h"
 
-#ifndef SFM_EPI_QG
-#define SFM_EPI_QG 2
-#endif
-#ifndef SFM_EPI_DEPTH
-#define SFM_EPI_DEPTH 1
-#endif
-// Ping-pong prefetch of the A fragments across row groups: measured 6 % SLOWER
-// on the <10,11> variant (200 bytes of spills at the 256-VGPR limit), neutral on
-// the smaller ones; kept as an experiment switch.
-#ifndef SFM_WIDE_BPREFETCH_MAX
-#define SFM_WIDE_BPREFETCH_MAX 20   // widest variant whose B dwords are double-buffered too
-#endif
-#ifndef SFM_WIDE_HALVES
-#define SFM_WIDE_HALVES 1   // search-window variants: 8 waves per CU, a row tile as two column halves
-#endif
-#ifndef SFM_WIDE_WAVES
-#define SFM_WIDE_WAVES 8    // waves of the search-window variants' one workgroup per CU (8 or 12)
-#endif
-#ifndef SFM_WIDE_TRIP
-#define SFM_WIDE_TRIP 2
-#endif
-#ifndef SFM_AF_PREFETCH
-#define SFM_AF_PREFETCH 0
-#endif
-// Row-group loop with the A chunk outermost and in-place prefetch (see the
-// kernel): the production order.  0 selects the round-1 order (B fragment
-// outermost, all LDS fragment loads at the loop head).
-#ifndef SFM_LOOP_CA_OUTER
-#define SFM_LOOP_CA_OUTER 1
-#endif
-// The waves of a workgroup take dy tiles from a shared longest-first list (LDS
-// counter) instead of a static deal: the four SIMDs do not run at the same
-// speed (each shares its matrix pipe with a wave of the other workgroup of the
-// CU), and with the static deal ~17 % of a workgroup's time was spent waiting
-// for its slowest wave at the end of every patch.
-// One LDS instruction per MFMA gap instead of a burst of four behind every
-// chunk (see the row-group loop).
-#ifndef SFM_LOOP_INTERLEAVE
-#define SFM_LOOP_INTERLEAVE 1
-#endif
-#ifndef SFM_DYNAMIC_TILES
-#define SFM_DYNAMIC_TILES 1
-#endif
-
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include <cstring>
@@ -127,9 +95,13 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
+constexpr size_t kLdsPerCu = 160 * 1024;
+// search-window variants: one workgroup per CU, two waves per SIMD (twelve spill and lose)
+constexpr int kWideWaves = 8;
+constexpr int kWideThreads = 64 * kWideWaves;
 constexpr int kPadTop = 16;     // zero rows above the pre patch in LDS
 constexpr int kPadBottom = 18;  // zero rows below
-constexpr int kMaxTilesPerWave = 24;
+constexpr int kMaxTileJobs = 96;   // capacity of MfmaArgs::order (dy tiles, or their column halves)
 // Row-loop variants of the correlation kernel: outer column tiles (each side)
 // left out when their bound allows it.  With 20 column tiles (P = 160) and an
 // NCC peak of 0.9+ the outer 4 qualify for most patches, the outer 3 for all.
@@ -167,6 +139,45 @@ struct PatchParams {  // written by the prep kernel, one per patch
 //   SQHI / SQLO  with s = VAL^2:  s = 128 (SQHI + 64) + SQLO on valid pixels
 enum Plane { kPlaneVal = 0, kPlaneValid = 1, kPlaneSqHi = 2, kPlaneSqLo = 3 };
 
+// The correlation kernel's state words in dynamic LDS, behind the two patches and the
+// aux arrays (MfmaArgs::r_bytes).  The kernel takes its pointers from this struct and
+// the host the launch size: the size decides the workgroups per CU.
+struct LdsTail {
+  // [0] float bits of the running maximum of the current surface, [1] hot-list fill
+  // count of the current patch, [2] next patch of the workgroup (queue), [3] tile
+  // counter of the current patch
+  int head[4];
+  float tb[kBoundStride];   // pruning bounds of the current patch (a.prune)
+  // Pruning state of the workgroup:
+  //   [0] (row tile << 8 | column tile) that held the maximum of the previous patch:
+  //       where the next patch is probed first
+  //   [1] bit mask of the row tiles pruned in the current patch
+  //   [2] anything pruned in the current patch?  [3] patches done  [4] probe this patch?
+  int best[8];
+  // Lazy stores, per patch: [0] row tiles that should be stored (requests of
+  // tiles that may be hot), [1] tiles finished, [2] tiles stored, [3] tiles
+  // claimed for recomputation
+  int lz[4];
+  float lz_tmax[31];        // maximum of finished tile p (tiles 0 .. 30)
+  int lz_prev;              // tile mask of what the previous patch needed
+  // Column side of the lazy stores: [0], [1] lowest / highest column tile that
+  // held a possibly hot element in this patch, [2], [3] the same of the previous
+  // patch of the workgroup
+  int lz_cq[4];
+  // outer column tiles row tile p dropped inside its row loop (0: none beyond the
+  // a-priori ones)
+  int lz_ks[32];
+  int lz_rows[31];          // first | last << 8 row (0 .. 15) of tile p with a possibly hot element
+  int pad[5];               // unused; keeps the launch size where it has always been
+};
+constexpr size_t kLdsTailHead = offsetof(LdsTail, tb);   // what the raw (masked) launch has
+static_assert(kLdsTailHead == 16 && offsetof(LdsTail, best) == 16 + 1024 &&
+                  offsetof(LdsTail, lz) == 1072 && offsetof(LdsTail, lz_tmax) == 1088 &&
+                  offsetof(LdsTail, lz_prev) == 1212 && offsetof(LdsTail, lz_cq) == 1216 &&
+                  offsetof(LdsTail, lz_ks) == 1232 && offsetof(LdsTail, lz_rows) == 1360 &&
+                  offsetof(LdsTail, pad) == 1484 && sizeof(LdsTail) == 16 + 1024 + 464,
+              "the LDS size of a launch decides the workgroups per CU");
+
 struct MfmaArgs {
   const unsigned char* img[2];
   int ishape[2][2];   // [side][y, x]
@@ -188,12 +199,9 @@ struct MfmaArgs {
   int ml;             // left margin of the post patch rows (bytes)
   int a_bytes, b_bytes;
   int r_bytes;        // aux arrays / reduction scratch behind the patches
-  // static tile schedule: tiles (dy tile indices) per wave
-  int tiles[kWaves][kMaxTilesPerWave];  // ints: scalar loads from the kernarg segment
-  int n_tiles[kWaves];
-  // dynamic tile schedule: all dy tiles, longest first; the waves of a
-  // workgroup draw from it through an LDS counter
-  int order[kWaves * kMaxTilesPerWave];
+  // tile schedule: all dy tiles, longest first; the waves of a workgroup draw
+  // from it through an LDS counter (ints: scalar loads from the kernarg segment)
+  int order[kMaxTileJobs];
   int n_order;
   // fused first-peak search (flow_field.py:238-262); see FusedPeaks
   int do_peaks;
@@ -257,7 +265,6 @@ struct MfmaArgs {
   // to run its epilogue first forms its 16 table rows from them and the int8 patches
   // in LDS, writes them into G (now a per-patch scratch in L2: ten kilobytes that the
   // same lanes read back at once) and runs the ordinary epilogue.
-  int lazy_g;
   int* c16;           // [B, c16_stride]: [2][Py / 16 + 1][Px] column sums, then T[Py + 1]
   long long c16_stride;
   int nq;             // column tiles of the kernel variant
@@ -399,6 +406,10 @@ __device__ __forceinline__ v4i load_16_bytes(const unsigned char* img, long long
 //      stored as two 16-byte pieces per lane (contiguous across the wave).
 // ---------------------------------------------------------------------------
 constexpr int kWidePrepWaves = 8;
+constexpr int kWidePrepColsPerLane = 8, kWidePrepMaxCols = 64 * kWidePrepColsPerLane;
+// static LDS of the kernel: per-wave reduction words and the column sums of every stripe
+constexpr size_t kWidePrepStaticLds =
+    sizeof(int) * (3 * kWidePrepWaves + kWidePrepWaves * kWidePrepMaxCols);
 __device__ __forceinline__ int wave_scan_incl(int v);   // (defined with the same-size prep pass)
 typedef int v4i_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -409,8 +420,9 @@ __global__ void __launch_bounds__(64 * kWidePrepWaves) mfma_prep_wide_kernel(Mfm
     a.clk[2] = a.clk[3] = a.clk[4] = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int red[3][kWidePrepWaves];
-  constexpr int kColsPerLane = 8, kMaxCols = 64 * kColsPerLane;
+  constexpr int kColsPerLane = kWidePrepColsPerLane, kMaxCols = kWidePrepMaxCols;
   __shared__ int stripe[kWidePrepWaves][kMaxCols];
+  static_assert(sizeof(red) + sizeof(stripe) == kWidePrepStaticLds, "the host sizes the launch by it");
   const int b = blockIdx.x, s = blockIdx.y;
   const int py = s == 0 ? a.P[0] : a.Q[0];
   const int px = s == 0 ? a.P[1] : a.Q[1];
@@ -629,7 +641,7 @@ struct PrepTables {
 // launch went away -- 19.25 vs 18.9 ms per pair.  The two workgroups of a CU do
 // not stay in anti-phase, so the extra VALU / LDS phase of a patch is not hidden
 // behind the other workgroup's matrix loop; it simply adds.  Removed again.
-// LAZY (MfmaArgs::lazy_g, its own instantiation): the pass never needs a pixel
+// LAZY (kModeSameExactLazyG, its own instantiation): the pass never needs a pixel
 // twice, so nothing is staged in LDS -- see the fused loop below.
 template <int WAVES, int ROWS, bool LAZY>
 __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
@@ -688,10 +700,7 @@ __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
     x0[s] = min(max(a.starts[s][b * 2 + 1], 0), W - px);
     img_bytes[s] = (long long)H * W;
   }
-#ifndef SFM_PREP_ITEMS
-#define SFM_PREP_ITEMS 4
-#endif
-  constexpr int kItems = SFM_PREP_ITEMS;  // items per thread and plane whose loads are in flight
+  constexpr int kItems = 4;  // items per thread and plane whose loads are in flight
   if constexpr (LAZY) {
     // LAZY: everything this pass needs of a pixel is a sum -- per row, per column
     // and band of 16 rows, per 16 x 16 block, minimum / maximum -- so the patches
@@ -704,7 +713,7 @@ __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
     // a second pass (a thread per row / per column) folds them into the tables
     // the staged form fills.  2 x Py / 8 x Px / 16 items (400 for 160 x 160).  The
     // same exact integers in the same tables: everything below is shared.  Py, Px
-    // multiples of 16 (host: lazy_g).
+    // multiples of 16 (host: choose_mode).
     const int NB = py >> 4, NC = px >> 4;
     const int per_side = 2 * NB * NC;
     // rowpart[s][y][chunk] = row sum (12 bits) | sum of squares << 12;
@@ -1151,10 +1160,7 @@ __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
     // so the lane that holds IA[yv][xv] also holds the matching IB value and a
     // row of G leaves the registers directly -- no transposition through LDS, no
     // intra-wave fences (the first version spent 1.8 k cycles per row on them).
-    int y_end = wave == kPrepWaves - 1 ? py + 1 : ra1;
-  #ifdef SFM_ABLATE_SWEEP   // timing experiment only (garbage tables): the prep pass without its sweep
-    y_end = ra0;
-  #endif
+    const int y_end = wave == kPrepWaves - 1 ? py + 1 : ra1;
     for (int yv = ra0; yv < y_end; ++yv) {
       const int yw = py - yv;
       // the pixels that move the column sums to row yv + 1: requested now, added
@@ -1387,11 +1393,9 @@ __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
 
 constexpr int kPrepWavesAlone = 8;   // bands of rows swept concurrently (stand-alone kernel)
 // LAZY: three workgroups per CU (51 KB of LDS each; <= 80 VGPRs at six waves per SIMD)
-#ifndef SFM_PREP_LB
-#define SFM_PREP_LB 6
-#endif
+constexpr int kPrepLazyWavesPerSimd = 6;
 template <bool LAZY>
-__global__ void __launch_bounds__(64 * kPrepWavesAlone, LAZY ? SFM_PREP_LB : 1)
+__global__ void __launch_bounds__(64 * kPrepWavesAlone, LAZY ? kPrepLazyWavesPerSimd : 1)
 mfma_prep_same_kernel(MfmaArgs a) {
   if (a.work_counter && blockIdx.x == 0 && threadIdx.x == 0)
     *a.work_counter = 0;  // the correlation kernel's patch queue
@@ -2518,7 +2522,7 @@ constexpr int kModeGeneral = 0, kModeSame = 1, kModeRaw = 2, kModeSameExact = 3;
 // decisions that reach the output are unchanged: bit-identical results.
 constexpr int kModeSameLazy = 4, kModeSameExactLazy = 5;
 // kModeSameExactLazy with the correction table built in the epilogue of the tiles
-// that are stored (MfmaArgs::lazy_g; Py a multiple of 16): no table G in memory.
+// that are stored (chosen by choose_mode; Py a multiple of 16): no table G in memory.
 constexpr int kModeSameExactLazyG = 6;
 
 // Inclusive add scan over the 16 lanes of a DPP row (the 16 columns of a tile).
@@ -2610,18 +2614,13 @@ __device__ __forceinline__ int next_patch(const MfmaArgs& a, int b, int* next_ld
 }
 
 template <int NCA, int NCE, int MODE>
-__global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_WAVES : kThreads,
+__global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
                                   NCA > 10 ? 1 : 2) xcorr_mfma_kernel(MfmaArgs a) {
+  // NCA <= 10: two workgroups of four waves per CU, each on its own patch; the waves of a
+  // workgroup draw the row tiles of that patch.
   // Search-window geometry (NCA > 10: pre patches 161 .. 320 wide against a post patch of up
-  // to 160, processor/flow.py:577,792-803).  The pre patch alone is up to 119 KB of LDS, so a
-  // CU holds ONE workgroup = one wave per SIMD -- which then owns the SIMD's whole register
-  // file: 512 registers per lane, the 25 .. 30 accumulator tiles of a row tile in the upper
-  // half (the compiler places them in AGPRs), the 15 .. 20 A fragments double-buffered in the
-  // lower one (the fragments of the next row group are in flight while the 165 .. 220 matrix
-  // instructions of this one issue).  kModeGeneral semantics; no pruning.  (That is the FIRST
-  // form, SFM_WIDE_HALVES=0; the default is the second one, WIDE8 below.)
-  // The other variants (NCA <= 10) run two workgroups of four waves per CU, each on its own
-  // patch; the waves of a workgroup draw the row tiles of that patch.
+  // to 160, processor/flow.py:577,792-803; kModeGeneral semantics, no pruning).  The pre patch
+  // alone is up to 119 KB of LDS, so a CU holds ONE workgroup, see WIDE8 below.
   constexpr bool LAZYG = MODE == kModeSameExactLazyG;
   constexpr bool SAME = MODE == kModeSame || MODE == kModeSameExact || MODE == kModeSameLazy ||
                         MODE == kModeSameExactLazy || LAZYG;
@@ -2629,11 +2628,11 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
   constexpr bool LAZY = MODE == kModeSameLazy || MODE == kModeSameExactLazy || LAZYG;
   constexpr bool RAW = MODE == kModeRaw;
   constexpr int NQ = NCA + NCE - 1;
-  // Search-window variants, second form (SFM_WIDE_HALVES, the default): the CU's one workgroup
+  // Search-window variants: the CU's one workgroup
   // has EIGHT waves (two per SIMD: a partner covers a wave's fragment round trips and runs
   // its matrix loop under the other's epilogue) and a tile job is one column HALF of a row
   // tile -- NQH accumulator tiles in plain VGPRs, the 12 .. 15 A chunks that reach them.
-  constexpr bool WIDE8 = NCA > 10 && MODE == kModeGeneral && SFM_WIDE_HALVES;
+  constexpr bool WIDE8 = NCA > 10 && MODE == kModeGeneral;
   constexpr int NQH = (NQ + 1) / 2;
   constexpr int kCq0 = NCE - 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2642,30 +2641,18 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
   unsigned char* A_lds = smem;
   unsigned char* B_lds = smem + a.a_bytes;
   float* R_lds = reinterpret_cast<float*>(smem + a.a_bytes + a.b_bytes);
-  // 16 bytes behind the aux arrays: running maximum of the current surface.
-  int* pmax_lds = reinterpret_cast<int*>(smem + a.a_bytes + a.b_bytes + a.r_bytes);
+  // Behind the aux arrays: the workgroup's state words (LdsTail; the raw mode has the head only).
+  LdsTail* tail = reinterpret_cast<LdsTail*>(smem + a.a_bytes + a.b_bytes + a.r_bytes);
+  int* pmax_lds = tail->head;   // running maximum of the current surface
   int* hot_lds = pmax_lds + 1;  // hot-list fill count of the current patch
-  float* tb_lds = reinterpret_cast<float*>(pmax_lds + 4);  // pruning bounds (a.prune)
-  // Pruning state of the workgroup, behind the bounds:
-  //   [0] (row tile << 8 | column tile) that held the maximum of the previous patch:
-  //       where the next patch is probed first
-  //   [1] bit mask of the row tiles pruned in the current patch
-  //   [2] anything pruned in the current patch?  [3] patches done  [4] probe this patch?
-  int* best_lds = reinterpret_cast<int*>(tb_lds + kBoundStride);
-  // Lazy stores, per patch: [0] row tiles that should be stored (requests of
-  // tiles that may be hot), [1] tiles finished, [2] tiles stored, [3] tiles
-  // claimed for recomputation; lz_tmax[p]: maximum of finished tile p
-  int* lz = best_lds + 8;
-  float* lz_tmax = reinterpret_cast<float*>(lz + 4);
-  int* lz_prev = reinterpret_cast<int*>(lz_tmax + 31);   // (tiles 0 .. 30) what the previous patch needed
-  // Column side of the lazy stores: lz_cq[0], [1] lowest / highest column tile that
-  // held a possibly hot element in this patch, [2], [3] the same of the previous
-  // patch of the workgroup; lz_ks[p]: outer column tiles row tile p dropped inside its
-  // row loop (0: none beyond the a-priori ones)
-  int* lz_cq = lz_prev + 1;
-  int* lz_ks = lz_cq + 4;
-  // lz_rows[p]: first | last << 8 row (0 .. 15) of tile p with a possibly hot element
-  int* lz_rows = lz_ks + 32;
+  float* tb_lds = tail->tb;     // pruning bounds (a.prune)
+  int* best_lds = tail->best;
+  int* lz = tail->lz;
+  float* lz_tmax = tail->lz_tmax;
+  int* lz_prev = &tail->lz_prev;
+  int* lz_cq = tail->lz_cq;
+  int* lz_ks = tail->lz_ks;
+  int* lz_rows = tail->lz_rows;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n = lane & 15, g = lane >> 4;
@@ -2675,7 +2662,7 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
   const long long probe_c0 = clock64(), probe_w0 = wall_clock64();
   // Zero the whole LDS image once: pad rows / margins stay zero afterwards.
   for (int i = threadIdx.x * 16; i < a.a_bytes + a.b_bytes;
-       i += (WIDE8 ? 64 * SFM_WIDE_WAVES : kThreads) * 16)
+       i += (WIDE8 ? kWideThreads : kThreads) * 16)
     *reinterpret_cast<v4i*>(smem + i) = v4i{0, 0, 0, 0};
 
   if (SAME && (a.prune || LAZY) && threadIdx.x == 0) {
@@ -2846,7 +2833,7 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
                              pp.c[0], A_lds, a.pa, kPadTop, 0, NCA};
       const StagePlane sb = {a.img[1], bytes1, a.ishape[1][1], pp.y0[1], pp.x0[1], Qy, Qx,
                              pp.c[1], B_lds, a.pb, 0, a.ml, (Qx + 15) / 16};
-      stage_patches<WIDE8 ? 64 * SFM_WIDE_WAVES : kThreads>(sa, sb, threadIdx.x);
+      stage_patches<WIDE8 ? kWideThreads : kThreads>(sa, sb, threadIdx.x);
       TICK(8)
     }
     if (threadIdx.x == 0) {
@@ -2909,7 +2896,6 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
     const float mua = pp.mu[0], mub = pp.mu[1];
     float muab = mua * mub;
     asm volatile("" : "+v"(muab));  // every global load so far has been consumed
-#ifndef SFM_NO_TOUCH
     if (SAME) {
       // Pull this patch's correction table G (written by the prep kernel, by now
       // in HBM / Infinity Cache) into this XCD's L2, one touch per 64-byte line.
@@ -2961,13 +2947,11 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
         }
       }
     }
-#endif
     const int* IA = (SAME || RAW) ? nullptr : a.integ[0] + b * a.integ_stride[0];
     const int* IB = (SAME || RAW) ? nullptr : a.integ[1] + b * a.integ_stride[1];
     const float* G = SAME ? a.gtab + (long long)b * Py * Px : nullptr;
     float* surf = a.surface + b * a.s_stride;
 
-#if SFM_DYNAMIC_TILES
     bool redo_phase = false;   // LAZY: the patch's tiles are finished, recompute what was missed
     for (;;) {
       int ti = 0, p = 0;
@@ -3031,13 +3015,6 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
         if ((old >> p) & 1) continue;   // another wave took it
         forced = true;
       }
-#else
-    const int n_my_tiles = __builtin_amdgcn_readfirstlane(a.n_tiles[wave]);
-    for (int ti = 0; ti < n_my_tiles; ++ti) {
-      const int p = __builtin_amdgcn_readfirstlane(a.tiles[wave][ti]);
-      constexpr bool forced = false;
-      static_assert(!LAZY, "lazy stores need the dynamic tile queue");
-#endif
       // (the tile's body is a block of its own: a `continue` inside it ends the tile; the
       // same code without the block gets another block layout and register allocation)
       do {
@@ -3195,25 +3172,14 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
       const unsigned char* ap =
           A_lds + (kPadTop + ylo + g + dy0 + n) * a.pa;
       const unsigned char* bp = B_lds + (ylo + g) * a.pb + (pos0 & ~3);
-      // One row group: the B dwords of THIS group and the A fragments of the
-      // NEXT group are requested together, then the NCA x NCE MFMAs run on the A
-      // fragments that were prefetched a group ago -- only the first B dwords
-      // are on the critical path at the loop head.  (The last prefetch reads up
-      // to 8 rows past the tile's last row: still inside the workgroup's LDS,
-      // never used.)
-      auto row_group = [&](const v4i* af, v4i* af_next, const unsigned char* ap_next,
-                           const unsigned char* bp_cur) {
+      // One row group of the general mode with up to ten A chunks: the B dwords are
+      // read, funnel-shifted into NCE fragments and each used against every A chunk.
+      auto row_group = [&](const v4i* af, const unsigned char* bp_cur) {
         unsigned d[4 * NCE + 1];
 #pragma unroll
         for (int j = 0; j < 4 * NCE + 1; ++j)
           d[j] = *reinterpret_cast<const unsigned*>(bp_cur + 4 * j);
-        if (af_next) {
-#pragma unroll
-          for (int ca = 0; ca < NCA; ++ca)
-            af_next[ca] = *reinterpret_cast<const v4i*>(ap_next + 16 * ca);
-        }
-        // (one read of the caller's array per chunk: with NCA x NCE uses per call site the
-        // double-buffered fragment arrays of the wide variants were left in scratch memory)
+        // (one read of the caller's array per chunk)
         v4i afl[NCA];
 #pragma unroll
         for (int ca = 0; ca < NCA; ++ca) afl[ca] = af[ca];
@@ -3232,44 +3198,8 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           }
         }
       };
-      // Search-window variants: the B dwords of the NEXT row group are requested with its A
-      // fragments, behind this group's own loads -- a lone wave per SIMD has no partner to
-      // cover the round trip at the head of a row group (measured 20.6 cycles per matrix
-      // instruction with the dwords loaded where they are used).
-      constexpr int kNDW = 4 * NCE + 1;
-      auto row_group_w = [&](const v4i* af, v4i* af_next, const unsigned char* ap_next,
-                             const unsigned* dc, unsigned* dn, const unsigned char* bp_next) {
-        if (af_next) {
-#pragma unroll
-          for (int j = 0; j < kNDW; ++j)
-            dn[j] = *reinterpret_cast<const unsigned*>(bp_next + 4 * j);
-#pragma unroll
-          for (int ca = 0; ca < NCA; ++ca)
-            af_next[ca] = *reinterpret_cast<const v4i*>(ap_next + 16 * ca);
-        }
-        v4i afl[NCA];
-        unsigned dl[kNDW];
-#pragma unroll
-        for (int ca = 0; ca < NCA; ++ca) afl[ca] = af[ca];
-#pragma unroll
-        for (int j = 0; j < kNDW; ++j) dl[j] = dc[j];
-#pragma unroll
-        for (int c = 0; c < NCE; ++c) {
-          v4i bf;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            bf[k] = static_cast<int>(
-                __builtin_amdgcn_alignbyte(dl[4 * c + k + 1], dl[4 * c + k], sh));
-#pragma unroll
-          for (int ca = 0; ca < NCA; ++ca) {
-            const int q = ca - c + cq0;
-            acc[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(afl[ca], bf, acc[q], 0,
-                                                           0, 0);
-          }
-        }
-      };
       // (the general P != Q epilogue needs the registers: old order there)
-      if constexpr (SFM_LOOP_CA_OUTER && MODE != kModeGeneral) {
+      if constexpr (MODE != kModeGeneral) {
         // Software-pipelined order: A chunk outer, B fragment inner.  All NCE B
         // fragments of the row group stay in registers (4 NCE VGPRs) and every A
         // fragment is reloaded IN PLACE for the next row group right after its
@@ -3437,7 +3367,6 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           bp += 4 * a.pb;
 #pragma unroll
           for (int ca = 0; ca < NCA; ++ca) {
-#if SFM_LOOP_INTERLEAVE
             // the register set of the PREVIOUS chunk is free now: its reload and
             // this chunk's share of the next B dwords can sit in the MFMA gaps
             // (one LDS instruction per gap) instead of in a burst behind them
@@ -3454,7 +3383,6 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
               for (int j = ca * kPerCa; j < (ca + 1) * kPerCa && j < kND; ++j)
                 dn[j] = *reinterpret_cast<const unsigned*>(bp + 4 * j);
             }
-#endif
 #pragma unroll
             for (int c = 0; c < NCE; ++c) {
               const int q = ca - c + cq0;
@@ -3468,7 +3396,6 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
                       __builtin_amdgcn_alignbyte(dn[4 * c + k + 1], dn[4 * c + k], sh));
               }
             }
-#if SFM_LOOP_INTERLEAVE
             if (ca == NCA - 1)  // the last chunk's set: nothing follows in this group
               af[ca % kW] =
                   *reinterpret_cast<const v4i*>(ap + 4 * a.pa + 16 * (ca + kW - NCA));
@@ -3498,18 +3425,6 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
               }
               static_assert(NCE - 4 <= 8, "extend the switch");
             }
-#else
-            if (ca + kW < NCA)
-              af[ca % kW] = *reinterpret_cast<const v4i*>(ap + 16 * (ca + kW));
-            else
-              af[ca % kW] =
-                  *reinterpret_cast<const v4i*>(ap + 4 * a.pa + 16 * (ca + kW - NCA));
-            if (ca < NCA - 1) {
-#pragma unroll
-              for (int j = ca * kPerCa; j < (ca + 1) * kPerCa && j < kND; ++j)
-                dn[j] = *reinterpret_cast<const unsigned*>(bp + 4 * j);
-            }
-#endif
             // keep the chunk order: the machine scheduler would otherwise sink
             // every prefetch to the end of the body (= no prefetch distance)
             __builtin_amdgcn_sched_barrier(0);
@@ -3581,6 +3496,7 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           constexpr int CA0 = Q0 - kCq0 > 0 ? Q0 - kCq0 : 0;
           constexpr int CA1 = Q1 - 1 < NCA - 1 ? Q1 - 1 : NCA - 1;
           constexpr int NC = CA1 - CA0 + 1;
+          constexpr int kNDW = 4 * NCE + 1;   // B dwords of a row group
           int n_pairs = 0;
           // (the A chunks of the next row group are requested behind this group's B dwords:
           // two register sets, swapped by unrolling two groups per trip)
@@ -3614,26 +3530,16 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
             ap += 4 * a.pa;
             bp += 4 * a.pb;
           };
-          if constexpr (SFM_WIDE_WAVES <= 8) {
-            v4i afA[NC], afB[NC];
+          v4i afA[NC], afB[NC];
 #pragma unroll
-            for (int i = 0; i < NC; ++i)
-              afA[i] = *reinterpret_cast<const v4i*>(ap + 16 * (CA0 + i));
-            int yy = ylo;
-            for (; yy + 4 < yhi; yy += 8) {
-              group(afA, afB);
-              group(afB, afA);
-            }
-            if (yy < yhi) group(afA, nullptr);
-          } else {   // three waves per SIMD (170 registers each): no second fragment set
-            for (int yy = ylo; yy < yhi; yy += 4) {
-              v4i af1[NC];
-#pragma unroll
-              for (int i = 0; i < NC; ++i)
-                af1[i] = *reinterpret_cast<const v4i*>(ap + 16 * (CA0 + i));
-              group(af1, nullptr);
-            }
+          for (int i = 0; i < NC; ++i)
+            afA[i] = *reinterpret_cast<const v4i*>(ap + 16 * (CA0 + i));
+          int yy = ylo;
+          for (; yy + 4 < yhi; yy += 8) {
+            group(afA, afB);
+            group(afB, afA);
           }
+          if (yy < yhi) group(afA, nullptr);
 #pragma unroll
           for (int c = 0; c < NCE; ++c)
 #pragma unroll
@@ -3645,44 +3551,13 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           half_rows(std::integral_constant<int, 1>{});
         else
           half_rows(std::integral_constant<int, 0>{});
-      } else if constexpr (NCA > 10 && NCA <= SFM_WIDE_BPREFETCH_MAX) {
-        v4i afA[NCA], afB[NCA];
-        unsigned dA[kNDW], dB[kNDW];
-#pragma unroll
-        for (int ca = 0; ca < NCA; ++ca)
-          afA[ca] = *reinterpret_cast<const v4i*>(ap + 16 * ca);
-#pragma unroll
-        for (int j = 0; j < kNDW; ++j) dA[j] = *reinterpret_cast<const unsigned*>(bp + 4 * j);
-        int yb0 = ylo;
-        for (; yb0 + 4 < yhi; yb0 += 8) {
-          row_group_w(afA, afB, ap + 4 * a.pa, dA, dB, bp + 4 * a.pb);
-          row_group_w(afB, afA, ap + 8 * a.pa, dB, dA, bp + 8 * a.pb);
-          ap += 8 * a.pa;
-          bp += 8 * a.pb;
-        }
-        if (yb0 < yhi) row_group_w(afA, nullptr, nullptr, dA, nullptr, nullptr);
-        mfma_issued += (long long)((yhi - ylo + 3) / 4) * (NCA * NCE);
-      } else if constexpr (SFM_AF_PREFETCH || NCA > 10) {
-        v4i afA[NCA], afB[NCA];
-#pragma unroll
-        for (int ca = 0; ca < NCA; ++ca)
-          afA[ca] = *reinterpret_cast<const v4i*>(ap + 16 * ca);
-        int yb0 = ylo;
-        for (; yb0 + 4 < yhi; yb0 += 8) {
-          row_group(afA, afB, ap + 4 * a.pa, bp);
-          row_group(afB, afA, ap + 8 * a.pa, bp + 4 * a.pb);
-          ap += 8 * a.pa;
-          bp += 8 * a.pb;
-        }
-        if (yb0 < yhi) row_group(afA, nullptr, nullptr, bp);
-        mfma_issued += (long long)((yhi - ylo + 3) / 4) * (NCA * NCE);
       } else {
         for (int yb0 = ylo; yb0 < yhi; yb0 += 4) {
           v4i af[NCA];
 #pragma unroll
           for (int ca = 0; ca < NCA; ++ca)
             af[ca] = *reinterpret_cast<const v4i*>(ap + 16 * ca);
-          row_group(af, nullptr, nullptr, bp);
+          row_group(af, bp);
           ap += 4 * a.pa;
           bp += 4 * a.pb;
         }
@@ -3951,7 +3826,7 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           // the regime every lane of both tiles is in (0 L, 1 M, 2 R: scalar table bases,
           // 32-bit byte offsets, no selects) or 3 (the one or two tiles a regime boundary
           // runs through: per-lane masks).
-          constexpr int kT = SFM_WIDE_TRIP;   // column tiles per trip (16 kT gathers in flight)
+          constexpr int kT = 2;   // column tiles per trip (16 kT gathers in flight)
           // (REG 0 .. 2: consecutive tiles are 16 columns = 64 bytes apart in every table row
           // and in the surface, so a trip forms its addresses once, for its first tile, and
           // reaches the others through the instructions' immediate offsets)
@@ -4138,7 +4013,7 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           unsigned gofs[4];                               // byte offsets of G[yv][xvb]
 #pragma unroll
           for (int r = 0; r < 4; ++r) gofs[r] = 4u * static_cast<unsigned>(grow[r] + xvb);
-          constexpr int kQG = SFM_EPI_QG;
+          constexpr int kQG = 2;   // output columns per gather group
           constexpr int kGroupsE = (NCA + kQG - 1) / kQG;
           float gb[2][kQG][4];
           float rca_e[NCA], rcb_e[NCA];
@@ -4166,12 +4041,10 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           };
           auto store4 = [&](int q, int r, float v) {
             if (q < col_skip || q >= NQ - col_skip) v = 0.f;  // column tile left out
-#ifndef SFM_ABLATE_STORE  // timing experiment: the kernel without its surface writes
             if constexpr (!LAZY)
               __builtin_nontemporal_store(
                   v, reinterpret_cast<float*>(reinterpret_cast<char*>(surf) +
                                               (static_cast<size_t>(rowp[r]) + 64u * q)));
-#endif
             tmax = fmaxf(tmax, v);
             acc[q][r] = __float_as_int(v);
           };
@@ -4221,8 +4094,8 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
           }
         } else {
         const bool paired = Px == 16 * NCA;
-        constexpr int kQG = SFM_EPI_QG;        // output columns per gather group
-        constexpr int kDepth = SFM_EPI_DEPTH;  // groups in flight ahead of the stores
+        constexpr int kQG = 2;     // output columns per gather group
+        constexpr int kDepth = 1;  // groups in flight ahead of the stores
         constexpr int kSlots = kDepth + 1;
         constexpr int kGroups = (NCA + kQG - 1) / kQG;
         auto xv_of = [&](int q) {
@@ -4256,12 +4129,10 @@ __global__ void __launch_bounds__((NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_
             corr = fmaf(fny[r], fnx, corr);
             float v = static_cast<float>(acc[q][r]) + corr;
             if (q < col_skip || q >= NQ - col_skip) v = 0.f;  // column tile left out
-#ifndef SFM_ABLATE_STORE  // timing experiment: the kernel without its surface writes
             if constexpr (!LAZY)
               __builtin_nontemporal_store(
                   v, reinterpret_cast<float*>(reinterpret_cast<char*>(surf) +
                                               (static_cast<size_t>(rowp[r]) + 64u * q)));
-#endif
             tmax = fmaxf(tmax, v);
             acc[q][r] = __float_as_int(v);
           }
@@ -4621,28 +4492,13 @@ Ws carve_ws(const SfmXcorrDesc* d, void* base) {
 template <int NCA, int NCE, int MODE>
 int launch_one(const MfmaArgs& a, int grid, size_t lds, hipStream_t st) {
   // (search-window variants: eight waves per workgroup, see WIDE8 in the kernel)
-  constexpr int kThreadsV = (NCA > 10 && SFM_WIDE_HALVES) ? 64 * SFM_WIDE_WAVES : kThreads;
-  static size_t attr_set = 0;
-  if (lds > attr_set) {
-    SFM_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&xcorr_mfma_kernel<NCA, NCE, MODE>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    attr_set = lds;
-  }
+  constexpr int kThreadsV = NCA > 10 ? kWideThreads : kThreads;
+  if (int rc = sfm::set_lds(&xcorr_mfma_kernel<NCA, NCE, MODE>, lds)) return rc;
   // Persistent grid: as many workgroups as the CUs hold at once (registers and
   // LDS decide: 2 per CU for 160-wide patches, 3-4 for the small variants).
-  static int per_cu = 0;
-  static size_t per_cu_lds = 0;
-  if (per_cu == 0 || per_cu_lds != lds) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &n, reinterpret_cast<const void*>(&xcorr_mfma_kernel<NCA, NCE, MODE>), kThreadsV,
-            lds) != hipSuccess || n < 1)
-      n = lds * 2 <= 160 * 1024 ? 2 : 1;
-    per_cu = n;
-    per_cu_lds = lds;
-  }
-  int wg_per_cu = per_cu;
+  int wg_per_cu = sfm::blocks_per_cu(
+      reinterpret_cast<const void*>(&xcorr_mfma_kernel<NCA, NCE, MODE>), kThreadsV, lds);
+  if (wg_per_cu < 1) wg_per_cu = lds * 2 <= kLdsPerCu ? 2 : 1;
   {
     // (a measurement switch; read per call so that a test can flip it)
     const int cap = sfm::measure_option_int("SFM_MFMA_MAX_WG_PER_CU", 0);
@@ -4702,8 +4558,7 @@ int launch_mode(int vi, const MfmaArgs& a, int mode, int grid, size_t lds,
   return sfm::fail(SFM_ERR_INVALID, "no MFMA variant");
 }
 
-// Geometry, image pointers, LDS layout and the static tile schedule shared by
-// every mode.
+// Geometry, image pointers, LDS layout and the tile schedule shared by every mode.
 int fill_common(const SfmXcorrDesc* d, const Layout& l, MfmaArgs* ap) {
   MfmaArgs& a = *ap;
   std::memset(&a, 0, sizeof(a));
@@ -4736,8 +4591,7 @@ int fill_common(const SfmXcorrDesc* d, const Layout& l, MfmaArgs* ap) {
   a.ml = l.ml;
   a.a_bytes = l.a_bytes;
   a.b_bytes = l.b_bytes;
-  // Static schedule: dy tiles sorted by the number of patch rows they visit,
-  // dealt to the 4 waves longest-first.
+  // Schedule: dy tiles sorted by the number of patch rows they visit, longest first.
   const int np = (a.S[0] + 15) / 16;
   std::vector<std::pair<int, int>> work;
   for (int p = 0; p < np; ++p) {
@@ -4753,7 +4607,7 @@ int fill_common(const SfmXcorrDesc* d, const Layout& l, MfmaArgs* ap) {
     return sfm::fail(SFM_ERR_INVALID, "too many dy tiles");
   a.n_order = static_cast<int>(work.size());
   for (size_t i = 0; i < work.size(); ++i) a.order[i] = work[i].second;
-  if (l.nca > 10 && SFM_WIDE_HALVES) {
+  if (l.nca > 10) {
     // search-window variants: a tile job is one column half of a row tile (p | half << 8)
     if (2 * work.size() > sizeof(a.order) / sizeof(a.order[0]))
       return sfm::fail(SFM_ERR_INVALID, "too many dy tiles");
@@ -4762,16 +4616,6 @@ int fill_common(const SfmXcorrDesc* d, const Layout& l, MfmaArgs* ap) {
       a.order[2 * i] = work[i].second;
       a.order[2 * i + 1] = work[i].second | (1 << 8);
     }
-  }
-  int load[kWaves] = {0, 0, 0, 0};
-  for (auto& t : work) {
-    int best = 0;
-    for (int k = 1; k < kWaves; ++k)
-      if (load[k] < load[best]) best = k;
-    if (a.n_tiles[best] >= kMaxTilesPerWave)
-      return sfm::fail(SFM_ERR_INVALID, "too many dy tiles");
-    a.tiles[best][a.n_tiles[best]++] = t.second;
-    load[best] += t.first + 1;  // + epilogue
   }
   return SFM_OK;
 }
@@ -4825,6 +4669,127 @@ MaskedWs carve_masked(const SfmXcorrDesc* d, void* base) {
   return w;
 }
 
+// --- mfma_i8_surface in steps ------------------------------------------------
+
+// Workspace pointers, the output surface and the measurement knobs.
+void fill_workspace(const Ws& w, float* surface, MfmaArgs* ap) {
+  MfmaArgs& a = *ap;
+  a.pp = w.pp;
+  a.integ[0] = w.integ[0];
+  a.integ[1] = w.integ[1];
+  a.integ_stride[0] = w.stride[0];
+  a.integ_stride[1] = w.stride[1];
+  a.gtab = w.gtab;
+  a.c16 = w.c16;
+  a.c16_stride = w.c16_stride;
+  a.aux = w.aux;
+  a.aux_n = w.aux_n;
+  a.tbound = w.tbound;  // read (not used) by every same-size launch
+  a.surface = surface;
+  a.work_counter = sfm::measure_option_on("SFM_MFMA_QUEUE") ? w.counter : nullptr;
+  a.clk = reinterpret_cast<long long*>(w.counter + 16);
+  a.prio_mode = sfm::measure_option_int("SFM_MFMA_PRIO", 0);
+}
+
+// Fused first-peak search: its buffers, and the exact pruning of dy tiles that
+// cannot matter to the peak statistics.
+void fill_peaks(const SfmXcorrDesc* d, const sfm::FusedPeaks& fp, bool same, const Variant& v,
+                MfmaArgs* ap) {
+  MfmaArgs& a = *ap;
+  a.do_peaks = 1;
+  a.threshold_rel = d->threshold_rel;
+  a.min_distance = d->min_distance;
+  a.cand_cap = fp.cand_cap;
+  a.idx1 = fp.idx1;
+  a.v1 = fp.v1;
+  a.zero_is_peak = fp.zero_is_peak;
+  a.cand_count = fp.cand_count;
+  a.cand_val = fp.cand_val;
+  a.cand_idx = fp.cand_idx;
+  a.bitmap = fp.bitmap;
+  a.group = fp.group;
+  a.bitmap_words = fp.bitmap_words;
+  a.hot_cap = fp.hot_cap;
+  a.hot_count = fp.hot_count;
+  a.hot_val = fp.hot_val;
+  a.hot_idx = fp.hot_idx;
+  a.skipmask = fp.skipmask;
+  a.guard = std::max(d->min_distance, 2 * d->peak_radius[1]);
+  a.guard_x = std::max(d->min_distance, 2 * d->peak_radius[2]);
+  a.nq = v.nca + v.nce - 1;
+  a.prune_k[0] = col_skip_lo(a.nq);
+  a.prune_k[1] = col_skip_hi(a.nq);
+  a.prune_k[2] = col_skip_2(a.nq);
+  a.prune_k[3] = col_skip_3(a.nq);
+  a.probe = sfm::measure_option_on("SFM_MFMA_PROBE");  // "0": no seed probe
+  a.count_tiles = sfm::profiling() ? 1 : 0;
+  // least number of row groups between two tests inside the row loop of the
+  // lazy modes ("0": no tests); each test schedules the next, see check_after
+  a.early = sfm::option_int("SFM_MFMA_EARLY", 1);
+  a.touch_all = sfm::measure_option_tri("SFM_MFMA_TOUCH_ALL") == 1;
+  a.narrow = sfm::option_int("SFM_MFMA_NARROW", 64);   // widest narrowing allowed (0: off)
+  if (a.early < 0 || a.P[0] > kEarlyRows) a.early = 0;
+  a.prune = same && prune_enabled() && a.n_order <= kBoundTiles &&
+            a.P[0] <= 16 * kBlkRows && a.P[1] <= 16 * kBlkCols &&
+            a.P[0] <= kBoundRows && d->threshold_rel > 0.f && d->threshold_rel <= 1.f &&
+            a.guard >= 0;
+}
+
+constexpr int mode_of(bool same, bool exact, bool lazy, bool lazy_g) {
+  return !same ? kModeGeneral
+         : exact ? (lazy_g ? kModeSameExactLazyG : lazy ? kModeSameExactLazy : kModeSameExact)
+                 : (lazy ? kModeSameLazy : kModeSame);
+}
+
+int choose_mode(const SfmXcorrDesc* d, const Variant& v, const MfmaArgs& a, bool same,
+                bool peaks) {
+  const bool exact = same && d->patch[2] == 16 * v.nca && exact_enabled();
+  // lazy surface stores: the flow path only (fused peak search: nobody else
+  // reads the surface), tile masks of 31 bits, SFM_MFMA_LAZY=0 switches it off
+  bool lazy = same && peaks && a.n_order <= 31 && a.skipmask != nullptr;
+  if (!sfm::option_on("SFM_MFMA_LAZY")) lazy = false;
+  // The correction table built in the epilogue of the tiles that are stored instead
+  // of by the prep kernel (kModeSameExactLazyG): pays where few tiles reach an
+  // epilogue, i.e. with the pruning on (the un-pruned launch, every tile finished,
+  // keeps the table).  SFM_MFMA_LAZYG=0: off.
+  const bool lazy_g = exact && lazy && a.prune && sfm::option_on("SFM_MFMA_LAZYG") &&
+                      a.P[0] % 16 == 0 && a.P[0] <= 160 && a.P[1] <= 160 && a.P[0] >= 32;
+  return mode_of(same, exact, lazy, lazy_g);
+}
+
+// Patch statistics, centres and correction tables of the mode.
+int launch_prep(const MfmaArgs& a, int mode, const Variant& v, hipStream_t st) {
+  const size_t pixels = (size_t)a.P[0] * a.P[1];
+  if (mode == kModeSameExactLazyG) {   // no pixels in LDS: the packed row / half-band column words
+    const size_t lazy_lds =
+        sizeof(unsigned) * (2 * (size_t)a.P[0] * (a.P[1] / 16) + 2 * 2 * (size_t)(a.P[0] / 16) * a.P[1]);
+    if (int rc = sfm::set_lds(&mfma_prep_same_kernel<true>, lazy_lds)) return rc;
+    hipLaunchKernelGGL(mfma_prep_same_kernel<true>, dim3(a.batch),
+                       dim3(64 * kPrepWavesAlone), lazy_lds, st, a);
+  } else if (mode != kModeGeneral) {
+    const size_t prep_lds = 2 * ((pixels + 15) & ~(size_t)15);
+    if (int rc = sfm::set_lds(&mfma_prep_same_kernel<false>, prep_lds)) return rc;
+    hipLaunchKernelGGL(mfma_prep_same_kernel<false>, dim3(a.batch),
+                       dim3(64 * kPrepWavesAlone), prep_lds, st, a);
+  } else {
+    // search-window variants: the wide prep pass (see mfma_prep_wide_kernel) where its
+    // padded LDS copy of a patch fits next to its static arrays; mfma_prep_kernel
+    // (pixels + its reduction words: within the eligibility bound) writes the same tables
+    const size_t wide_lds = (size_t)a.P[0] * (16 * ((a.P[1] + 15) / 16) + 16);
+    if (v.nca > 10 && a.P[1] <= kWidePrepMaxCols &&
+        wide_lds + kWidePrepStaticLds <= kLdsPerCu) {
+      if (int rc = sfm::set_lds(&mfma_prep_wide_kernel, wide_lds)) return rc;
+      hipLaunchKernelGGL(mfma_prep_wide_kernel, dim3(a.batch, 2), dim3(64 * kWidePrepWaves),
+                         wide_lds, st, a);
+    } else {
+      if (int rc = sfm::set_lds(&mfma_prep_kernel, pixels)) return rc;
+      hipLaunchKernelGGL(mfma_prep_kernel, dim3(a.batch, 2), dim3(kThreads), pixels, st, a);
+    }
+  }
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
+}
+
 }  // namespace
 
 namespace sfm {
@@ -4845,10 +4810,10 @@ bool mfma_i8_eligible(const SfmXcorrDesc* d) {
     if (d->pre_mask || d->post_mask) return false;
     if ((long long)py * px > 140 * 1024) return false;
     const Layout l = make_layout(d, kVariants[vi]);
-    if ((size_t)l.a_bytes + l.b_bytes + 8 * 1024 > 160 * 1024) return false;
+    if ((size_t)l.a_bytes + l.b_bytes + 8 * 1024 > kLdsPerCu) return false;
   }
   if ((long long)qy * qx * 16384 > 0x7fffffffLL) return false;  // int32 sums
-  if ((py + qy - 1 + 15) / 16 > kWaves * kMaxTilesPerWave) return false;
+  if ((py + qy - 1 + 15) / 16 > kMaxTileJobs) return false;
   // (the staging loads are 16 bytes wide and clamped into the image)
   if ((long long)d->pre_shape[1] * d->pre_shape[2] < 16 ||
       (long long)d->post_shape[1] * d->post_shape[2] < 16)
@@ -4877,137 +4842,22 @@ int mfma_i8_surface(const SfmXcorrDesc* d, void* ws_base, float* surface,
   const int vi = pick_variant(d->patch[2], d->post_patch[2]);
   if (vi < 0) return fail(SFM_ERR_INVALID, "patch too wide for the MFMA path");
   const Layout l = make_layout(d, kVariants[vi]);
-  Ws w = carve_ws(d, ws_base);
+  const Ws w = carve_ws(d, ws_base);
   MfmaArgs a;
   if (int rc = fill_common(d, l, &a)) return rc;
-  a.pp = w.pp;
+  fill_workspace(w, surface, &a);
   const bool same = same_size(d);
-  a.integ[0] = w.integ[0];
-  a.integ[1] = w.integ[1];
-  a.integ_stride[0] = w.stride[0];
-  a.integ_stride[1] = w.stride[1];
-  a.gtab = w.gtab;
-  a.c16 = w.c16;
-  a.c16_stride = w.c16_stride;
-  a.aux = w.aux;
-  a.aux_n = w.aux_n;
-  a.surface = surface;
-  {
-    a.work_counter = sfm::measure_option_on("SFM_MFMA_QUEUE") ? w.counter : nullptr;
-    a.clk = reinterpret_cast<long long*>(w.counter + 16);
-    a.prio_mode = sfm::measure_option_int("SFM_MFMA_PRIO", 0);
-  }
-  if (fp) {
-    a.do_peaks = 1;
-    a.threshold_rel = d->threshold_rel;
-    a.min_distance = d->min_distance;
-    a.cand_cap = fp->cand_cap;
-    a.idx1 = fp->idx1;
-    a.v1 = fp->v1;
-    a.zero_is_peak = fp->zero_is_peak;
-    a.cand_count = fp->cand_count;
-    a.cand_val = fp->cand_val;
-    a.cand_idx = fp->cand_idx;
-    a.bitmap = fp->bitmap;
-    a.group = fp->group;
-    a.bitmap_words = fp->bitmap_words;
-    a.hot_cap = fp->hot_cap;
-    a.hot_count = fp->hot_count;
-    a.hot_val = fp->hot_val;
-    a.hot_idx = fp->hot_idx;
-    a.skipmask = fp->skipmask;
-    // exact pruning of dy tiles that cannot matter to the peak statistics
-    a.tbound = w.tbound;
-    a.guard = std::max(d->min_distance, 2 * d->peak_radius[1]);
-    a.guard_x = std::max(d->min_distance, 2 * d->peak_radius[2]);
-    a.nq = kVariants[vi].nca + kVariants[vi].nce - 1;
-    a.prune_k[0] = col_skip_lo(a.nq);
-    a.prune_k[1] = col_skip_hi(a.nq);
-    a.prune_k[2] = col_skip_2(a.nq);
-    a.prune_k[3] = col_skip_3(a.nq);
-    a.probe = sfm::measure_option_on("SFM_MFMA_PROBE");  // "0": no seed probe
-    a.count_tiles = sfm::profiling() ? 1 : 0;
-    {
-      // least number of row groups between two tests inside the row loop of the
-      // lazy modes ("0": no tests); each test schedules the next, see check_after
-      a.early = sfm::option_int("SFM_MFMA_EARLY", 1);
-      a.touch_all = sfm::measure_option_tri("SFM_MFMA_TOUCH_ALL") == 1;
-      a.narrow = sfm::option_int("SFM_MFMA_NARROW", 64);   // widest narrowing allowed (0: off)
-      if (a.early < 0 || a.P[0] > kEarlyRows) a.early = 0;
-    }
-    a.prune = same && prune_enabled() && a.n_order <= kBoundTiles &&
-              a.P[0] <= 16 * kBlkRows && a.P[1] <= 16 * kBlkCols &&
-              a.P[0] <= kBoundRows && d->threshold_rel > 0.f && d->threshold_rel <= 1.f &&
-              a.guard >= 0;
-  }
-  if (!a.tbound) a.tbound = w.tbound;  // read (not used) by every same-size launch
-  const bool exact = same && d->patch[2] == 16 * kVariants[vi].nca && exact_enabled();
-  // lazy surface stores: the flow path only (fused peak search: nobody else
-  // reads the surface), tile masks of 31 bits, SFM_MFMA_LAZY=0 switches it off
-  bool lazy = same && fp != nullptr && a.n_order <= 31 && a.skipmask != nullptr;
-  if (!sfm::option_on("SFM_MFMA_LAZY")) lazy = false;
-  // The correction table built in the epilogue of the tiles that are stored instead
-  // of by the prep kernel (kModeSameExactLazyG): pays where few tiles reach an
-  // epilogue, i.e. with the pruning on (the un-pruned launch, every tile finished,
-  // keeps the table).  SFM_MFMA_LAZYG=0: off.
-  a.lazy_g = exact && lazy && a.prune && sfm::option_on("SFM_MFMA_LAZYG") &&
-             a.P[0] % 16 == 0 && a.P[0] <= 160 && a.P[1] <= 160 && a.P[0] >= 32;
+  if (fp) fill_peaks(d, *fp, same, kVariants[vi], &a);
+  const int mode = choose_mode(d, kVariants[vi], a, same, fp != nullptr);
   // Region behind the patches: the four 1-D correction arrays, reused as the
-  // arg-max scratch of the fused peak search, then the running-max word.
+  // arg-max scratch of the fused peak search, then the state words (LdsTail).
   size_t r_bytes = same ? (size_t)4 * w.aux_n * 4 : 0;
   r_bytes = std::max(r_bytes, (size_t)kThreads * 8);
   r_bytes = (r_bytes + 15) / 16 * 16;
   a.r_bytes = static_cast<int>(r_bytes);
-  if (same) {
-    const size_t prep_lds = 2 * (((size_t)a.P[0] * a.P[1] + 15) & ~(size_t)15);
-    static size_t prep_attr = 0;
-    if (!a.lazy_g && prep_lds > prep_attr) {
-      SFM_HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(&mfma_prep_same_kernel<false>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(prep_lds)));
-      prep_attr = prep_lds;
-    }
-    if (a.lazy_g) {   // no pixels in LDS: the packed row / half-band column words
-      const size_t lazy_lds =
-          sizeof(unsigned) * (2 * (size_t)a.P[0] * (a.P[1] / 16) + 2 * 2 * (size_t)(a.P[0] / 16) * a.P[1]);
-      hipLaunchKernelGGL(mfma_prep_same_kernel<true>, dim3(d->batch),
-                         dim3(64 * kPrepWavesAlone), lazy_lds, st, a);
-    }
-    else
-      hipLaunchKernelGGL(mfma_prep_same_kernel<false>, dim3(d->batch),
-                         dim3(64 * kPrepWavesAlone), prep_lds, st, a);
-  } else {
-    const size_t prep_lds = (size_t)a.P[0] * a.P[1];
-    static size_t prep_gen_attr = 0;
-    if (prep_lds > 48 * 1024 && prep_lds > prep_gen_attr) {
-      SFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mfma_prep_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        static_cast<int>(prep_lds)));
-      prep_gen_attr = prep_lds;
-    }
-    if (kVariants[vi].nca > 10 && a.P[1] <= 512) {
-      // search-window variants: the wide prep pass (see mfma_prep_wide_kernel)
-      const size_t wide_lds = (size_t)a.P[0] * (16 * ((a.P[1] + 15) / 16) + 16);
-      static size_t wide_attr = 0;
-      if (wide_lds > wide_attr) {
-        SFM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mfma_prep_wide_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          static_cast<int>(wide_lds)));
-        wide_attr = wide_lds;
-      }
-      hipLaunchKernelGGL(mfma_prep_wide_kernel, dim3(d->batch, 2), dim3(64 * kWidePrepWaves),
-                         wide_lds, st, a);
-    } else
-    hipLaunchKernelGGL(mfma_prep_kernel, dim3(d->batch, 2), dim3(kThreads),
-                       prep_lds, st, a);
-  }
-  SFM_LAUNCH_CHECK();
-  const size_t lds = (size_t)l.a_bytes + l.b_bytes + r_bytes + 16 + 4 * kBoundStride + 48 + 128 + 160 + 128;
+  if (int rc = launch_prep(a, mode, kVariants[vi], st)) return rc;
+  const size_t lds = (size_t)l.a_bytes + l.b_bytes + r_bytes + sizeof(LdsTail);
   const int grid = d->batch;  // capped to the resident workgroups in launch_one
-  const int mode = !same ? kModeGeneral
-                   : exact ? (a.lazy_g ? kModeSameExactLazyG
-                                       : lazy ? kModeSameExactLazy : kModeSameExact)
-                           : (lazy ? kModeSameLazy : kModeSame);
   if (int rc = launch_mode(vi, a, mode, grid, lds, st)) return rc;
   if (fp) {
     hipLaunchKernelGGL(mfma_first_peak_kernel, dim3((d->batch + kWaves - 1) / kWaves), dim3(kThreads), 0, st, a);
@@ -5047,7 +4897,7 @@ int mfma_i8_masked(const SfmXcorrDesc* d, void* ws_base, float* surface,
   SFM_HIP_CHECK(hipMemsetAsync(w.ov_lb, 0, w.n_groups * sizeof(int), st));
   size_t r_bytes = (size_t)kThreads * 8;
   a.r_bytes = static_cast<int>(r_bytes);
-  const size_t lds = (size_t)l.a_bytes + l.b_bytes + r_bytes + 16;
+  const size_t lds = (size_t)l.a_bytes + l.b_bytes + r_bytes + kLdsTailHead;
   MaskedFastArgs g;
   std::memset(&g, 0, sizeof(g));
   g.pp = w.pp;

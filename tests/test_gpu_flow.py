@@ -303,8 +303,8 @@ def test_flow_field_empty_selection_and_single_patch(gpu):
     (200, 320, 160, 96), (161, 161, 160, 160),
 ])
 def test_search_window_mfma_matches_direct_kernel(gpu, py, px, qy, qx):
-  """The wide variants of the int8 kernel (one wave per SIMD, accumulators in the upper
-  register file) against the float direct kernel: identical peaks, statistics within the
+  """The wide variants of the int8 kernel (eight waves per CU, a tile job is one column
+  half of a row tile) against the float direct kernel: identical peaks, statistics within the
   float kernel's tolerance; starts that overshoot the image on every side (clamped like
   lax.dynamic_slice, flow_field.py:320-325), per-patch and fixed means."""
   from sofima_amd import flow_field
@@ -333,6 +333,42 @@ def test_search_window_mfma_matches_direct_kernel(gpu, py, px, qy, qx):
     # (the float kernel sums up to 102 400 products per output here, 4 x the 160^2 case the
     # VS_F32_KERNEL criterion was sized on: window minimum to 8e-5 x |peak|.  The oracle
     # comparison of the same kernel is test_search_window_flow_vs_oracle.)
+    check_sharpness(got[ok, 2], ref[ok, 2], inv_atol=8e-5, inv_from=0.0)
+    np.testing.assert_allclose(got[:, 3], ref[:, 3], rtol=2e-4, atol=1e-6)
+
+
+def test_search_window_tall_patch_prep_fits_lds(gpu):
+  """A 597 x 240 pre patch against a 16 x 16 post patch is eligible for the matrix path
+  (597 * 240 = 143 280 <= 143 360 pixels; the correlation kernel's two patches + 8 KB =
+  163 584 <= 163 840 bytes), but the wide prep pass would need 597 * (16 * 15 + 16) =
+  152 832 dynamic + 16 480 static bytes of LDS, more than the 160 KB of a CU: the plain prep
+  kernel (143 280 + 3 072 bytes) has to take such patches.  Assertions and tolerances of
+  test_search_window_mfma_matches_direct_kernel (each output sums 256 products here, far
+  fewer than the 102 400 those were sized for)."""
+  from sofima_amd import flow_field
+  from scipy import ndimage
+  py, px, qy, qx = 597, 240, 16, 16
+  rng = np.random.default_rng(py * 1000 + px)
+  h, w = 640, 272
+  base = ndimage.gaussian_filter(rng.standard_normal((h + 8, w + 8)), 1.5)
+  base = ((base - base.min()) / (base.max() - base.min()) * 255).astype(np.uint8)
+  pre = base[4:4 + h, 4:4 + w].copy()
+  post = base[6:6 + h, 1:1 + w].copy()
+  post[::7, ::5] += 3
+  # every start overshoots the image on some side (clamped like lax.dynamic_slice)
+  starts = np.array([[-4, -3], [h - py + 5, w - px + 3], [-2, w - px + 4]])
+  b = len(starts)
+  post_starts = starts + np.array([(py - qy) // 2, (px - qx) // 2]) + rng.integers(-9, 10, (b, 2))
+  kw = dict(min_distance=2, threshold_rel=0.5, peak_radius=5,
+            post_patch_size=(qy, qx), post_starts=post_starts)
+  for mean in (None, 117.5):
+    ref = flow_field.batched_xcorr_peaks(pre, post, None, None, (py, px), starts,
+                                         mean, method=1, **kw)
+    got = flow_field.batched_xcorr_peaks(pre, post, None, None, (py, px), starts,
+                                         mean, method=2, **kw)
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(ref))
+    np.testing.assert_array_equal(got[:, :2], ref[:, :2])
+    ok = np.isfinite(ref[:, 2])
     check_sharpness(got[ok, 2], ref[ok, 2], inv_atol=8e-5, inv_from=0.0)
     np.testing.assert_allclose(got[:, 3], ref[:, 3], rtol=2e-4, atol=1e-6)
 
@@ -836,6 +872,55 @@ def test_concurrent_python_threads(gpu):
       t.join()
     assert not errs, errs
     for g, w in zip(got, want):
+      np.testing.assert_array_equal(g, w)
+
+
+@pytest.mark.gpu
+def test_two_patch_geometries_from_two_threads(gpu):
+  """Un-masked flow on the matrix cores at two patch geometries (48 x 48 and 160 x 160,
+  8 patches each: two kernel variants, two LDS sizes, one above the 48 KB a kernel gets
+  without asking), called back to back from two threads at once, each thread alternating
+  between the two in the opposite order: each call returns the bits of the same call made
+  alone.  The threads run FIRST, so the first launches of both geometries -- the ones that
+  raise the dynamic-LDS limit and fill the occupancy table, kept per device and kernel
+  behind a lock -- are the concurrent ones; the single-thread results are taken afterwards."""
+  import threading
+  from scipy import ndimage
+  from sofima_amd import flow_field
+  rng = np.random.default_rng(48160)
+  base = ndimage.gaussian_filter(rng.standard_normal((408, 408)), 1.5)
+  base = ((base - base.min()) / (base.max() - base.min()) * 255).astype(np.uint8)
+  pre = np.ascontiguousarray(base[4:404, 4:404])
+  post = np.ascontiguousarray(base[6:406, 1:401])
+
+  def job(patch, seed):
+    starts = np.random.default_rng(seed).integers(-4, 400 - patch + 5, (8, 2))
+    return lambda: flow_field.batched_xcorr_peaks(
+        pre, post, None, None, (patch, patch), starts, None, min_distance=2,
+        threshold_rel=0.5, peak_radius=5, method=2)
+
+  jobs = [job(48, 1), job(160, 2)]
+  got = [[], []]   # per job: the results of every call of it, from either thread
+  errs = []
+
+  def run(i):
+    try:
+      for k in range(4):
+        j = (i + k) % 2
+        got[j].append(jobs[j]())
+    except Exception as e:  # pylint: disable=broad-except
+      errs.append(e)
+
+  threads = [threading.Thread(target=run, args=(i,)) for i in range(len(jobs))]
+  for t in threads:
+    t.start()
+  for t in threads:
+    t.join()
+  assert not errs, errs
+  want = [j() for j in jobs]
+  for gs, w in zip(got, want):
+    assert len(gs) == 4
+    for g in gs:
       np.testing.assert_array_equal(g, w)
 
 
