@@ -252,7 +252,11 @@ typedef struct SfmFlowScatterDesc {
 int sfm_flow_scatter(const SfmFlowScatterDesc* desc);
 
 /* Stand-alone peak statistics, replaces _batched_peaks (flow_field.py:205-275)
- * for a caller-provided batch of surfaces. */
+ * for a caller-provided batch of surfaces.  A surface that holds a NaN or a
+ * +inf has no peak (a NaN row; its first-peak index counts as 0 in the batch's
+ * suppression set); the sharpness window is clipped to a surface smaller than
+ * 2 * peak_radius + 1.  SFM_ERR_INVALID for a negative min_distance or a
+ * negative peak_radius on a used axis. */
 typedef struct SfmPeaksDesc {
   int32_t ndim;
   int32_t batch;

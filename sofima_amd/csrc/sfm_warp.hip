@@ -197,8 +197,9 @@ struct NdWarpArgs {
 };
 
 // scipy NI_GeometricTransform, order 1, mode "constant", cval 0: outside
-// [0, len - 1] on any axis -> 0; taps beyond the last sample carry weight 0 and
-// are read from the last sample.
+// [0, len - 1] on any axis, NaN included -> 0; the tap beyond the last sample
+// (coordinate exactly len - 1) carries weight 0 and is read mirrored, from
+// len - 2, as SciPy's edge mapping does: 0 x inf and 0 x NaN there are NaN.
 template <int DIM, typename T>
 __device__ __forceinline__ double linear_sample(const T* __restrict__ a, const int* shape,
                                                 const double* c) {
@@ -214,7 +215,7 @@ __device__ __forceinline__ double linear_sample(const T* __restrict__ a, const i
 #pragma unroll
   for (int d = 0; d < DIM; ++d) {
     const int len = shape[3 - DIM + d];
-    if (c[d] < 0.0 || c[d] > static_cast<double>(len - 1)) return 0.0;
+    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
     const double fl = floor(c[d]);
     const double t = c[d] - fl;
     w[d][0] = 1.0 - t;
@@ -230,7 +231,7 @@ __device__ __forceinline__ double linear_sample(const T* __restrict__ a, const i
       const int bit = (tap >> (DIM - 1 - d)) & 1;
       const int len = shape[3 - DIM + d];
       long long i = base[d] + bit;
-      i = i > len - 1 ? len - 1 : i;
+      if (i > len - 1) i = len > 1 ? len - 2 : 0;
       idx += i * step[d];
     }
     double coeff = static_cast<double>(a[idx]);
@@ -248,7 +249,7 @@ __device__ __forceinline__ double nearest_sample(const T* __restrict__ a, const 
 #pragma unroll
   for (int d = DIM - 1; d >= 0; --d) {
     const int len = shape[3 - DIM + d];
-    if (c[d] < 0.0 || c[d] > static_cast<double>(len - 1)) return 0.0;
+    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
     long long i = static_cast<long long>(floor(c[d] + 0.5));
     i = i > len - 1 ? len - 1 : i;
     idx += i * pitch;

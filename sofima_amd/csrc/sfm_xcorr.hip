@@ -731,13 +731,22 @@ __device__ __forceinline__ void sweep_rows_any(const float* s, const PeakArgs& p
     sweep_rows<8>(s, p, r0, rows, body);
 }
 
+// NANS: a NaN element makes the maximum NaN, as the reference's img.max() does
+// (fmaxf drops it).  Only the stand-alone entry asks for it: the surfaces of the
+// fused producers are sums of integer products and hold none.
+template <bool NANS = false>
 __device__ float surface_max(const float* s, const PeakArgs& p, float* lv,
                              int* li, int r0 = 0, int r1 = -1) {
   const int rows = r1 < 0 ? p.S[0] * p.S[1] : r1;
   float mx = -INFINITY;
-  sweep_rows_any(s, p, r0, rows, [&](int, int, float v) { mx = fmaxf(mx, v); });
+  int bad = 0;
+  sweep_rows_any(s, p, r0, rows, [&](int, int, float v) {
+    mx = fmaxf(mx, v);
+    if (NANS) bad |= v != v;
+  });
   int dummy = 0;
   block_argmax(&mx, &dummy, lv, li);
+  if (NANS && __syncthreads_or(bad)) mx = NAN;
   return mx;
 }
 
@@ -755,12 +764,15 @@ __device__ void for_each_peak(const float* s, const PeakArgs& p, float thr, F fn
   });
 }
 
+// (a NaN maximum makes the threshold NaN: nothing exceeds it, the row is NaN and
+// its first-peak index 0 -- the reference's arg-max of an all -inf row)
+template <bool NANS>
 __global__ void __launch_bounds__(kBlock) peaks_first_kernel(PeakArgs p) {
   __shared__ float lv[kBlock];
   __shared__ int li[kBlock];
   const int b = blockIdx.x;
   const float* s = p.surf + b * p.bstride;
-  const float mx = surface_max(s, p, lv, li);
+  const float mx = surface_max<NANS>(s, p, lv, li);
   const float thr = p.threshold_rel * mx;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
@@ -818,14 +830,18 @@ __device__ __forceinline__ void chunk_rows(const PeakArgs& p, int b, int* r0, in
   *r1 = lo + min(rows, static_cast<int>(blockIdx.x) * per + per);
 }
 
+// (a NaN maximum travels as the largest ordered word, above +inf: it wins every
+// merge and ord_float gives a NaN back)
+template <bool NANS>
 __global__ void __launch_bounds__(kBlock) peaks_max_kernel(PeakArgs p) {
   __shared__ float lv[kBlock];
   __shared__ int li[kBlock];
   const int b = blockIdx.y;
   int r0, r1;
   chunk_rows(p, b, &r0, &r1);
-  const float mx = surface_max(p.surf + b * p.bstride, p, lv, li, r0, r1);
-  if (threadIdx.x == 0 && r1 > r0) atomicMax(&p.smax[b], ord_bits(mx));
+  const float mx = surface_max<NANS>(p.surf + b * p.bstride, p, lv, li, r0, r1);
+  if (threadIdx.x == 0 && r1 > r0)
+    atomicMax(&p.smax[b], NANS && mx != mx ? 0xffffffffu : ord_bits(mx));
 }
 
 __global__ void __launch_bounds__(kBlock) peaks_scan_kernel(PeakArgs p) {
@@ -1099,7 +1115,8 @@ int run_peaks(const PeakWs& w, char* ws_base, const float* surf, int pitch,
               int min_distance, float threshold_rel, const int* radius,
               float* out, hipStream_t st, bool first_pass_done = false,
               bool smax_done = false, const unsigned int* live_ovmax = nullptr,
-              const int* live_geo = nullptr, bool use_blkmax = false) {
+              const int* live_geo = nullptr, bool use_blkmax = false,
+              bool nans = false) {
   PeakArgs p;
   p.blkmax = use_blkmax ? w.blkmax : nullptr;
   p.blk_rows = sfm::kMaskedBlkRows;
@@ -1144,16 +1161,22 @@ int run_peaks(const PeakWs& w, char* ws_base, const float* surf, int pitch,
       const long long rows = (long long)S[0] * S[1];
       const int chunks = static_cast<int>(std::min<long long>(
           std::min<long long>(rows, 1024), std::max<long long>(1, sn >> 15)));
-      if (!smax_done)
-        hipLaunchKernelGGL(peaks_max_kernel, dim3(chunks, batch), dim3(kBlock), 0, st, p);
+      if (!smax_done) {
+        if (nans)
+          hipLaunchKernelGGL(peaks_max_kernel<true>, dim3(chunks, batch), dim3(kBlock), 0, st, p);
+        else
+          hipLaunchKernelGGL(peaks_max_kernel<false>, dim3(chunks, batch), dim3(kBlock), 0, st, p);
+      }
       if (p.blkmax)   // one workgroup per surface, at most 4096 of them
         hipLaunchKernelGGL(peaks_scan_kernel, dim3(1, std::min(batch, 4096)), dim3(kBlock), 0, st, p);
       else
         hipLaunchKernelGGL(peaks_scan_kernel, dim3(chunks, batch), dim3(kBlock), 0, st, p);
       hipLaunchKernelGGL(peaks_first_finish_kernel, dim3((batch + kBlock - 1) / kBlock),
                          dim3(kBlock), 0, st, p);
+    } else if (nans) {
+      hipLaunchKernelGGL(peaks_first_kernel<true>, dim3(batch), dim3(kBlock), 0, st, p);
     } else {
-      hipLaunchKernelGGL(peaks_first_kernel, dim3(batch), dim3(kBlock), 0, st, p);
+      hipLaunchKernelGGL(peaks_first_kernel<false>, dim3(batch), dim3(kBlock), 0, st, p);
     }
     SFM_LAUNCH_CHECK();
   }
@@ -1590,16 +1613,24 @@ int sfm_peaks(const SfmPeaksDesc* d, float* peaks) {
   }
   if (sn > 0x7fffffffLL)
     return sfm::fail(SFM_ERR_INVALID, "surface too large for int32 indices");
+  if (d->min_distance < 0)
+    return sfm::fail(SFM_ERR_INVALID, "min_distance must be >= 0, got %d", d->min_distance);
+  for (int i = 3 - d->ndim; i < 3; ++i)
+    if (d->peak_radius[i] < 0)
+      return sfm::fail(SFM_ERR_INVALID, "peak_radius must be >= 0, got %d", d->peak_radius[i]);
   sfm::Carver c(d->workspace);
   PeakWs w = carve_peaks(c, d->batch, sn);
   if (!d->workspace || d->workspace_bytes < w.bytes)
     return sfm::fail(SFM_ERR_WORKSPACE, "peaks workspace needs %zu bytes, got %zu",
                      w.bytes, d->workspace_bytes);
+  // caller-supplied surfaces may hold NaN: the only entry that asks for the
+  // NaN-propagating surface maximum
   return run_peaks(w, static_cast<char*>(d->workspace), d->surface, d->shape[2],
                    sn, d->ndim, d->shape, sn, d->batch, d->center_offset,
                    d->min_distance,
                    d->threshold_rel, d->peak_radius, peaks,
-                   static_cast<hipStream_t>(d->stream));
+                   static_cast<hipStream_t>(d->stream), false, false, nullptr, nullptr,
+                   false, true);
 }
 
 }  // extern "C"

@@ -390,8 +390,15 @@ def _batched_peaks(img, center_offset, min_distance: int, threshold_rel: float,
   """Peak statistics for a batch of correlation surfaces -> [b, dim + 2].
 
   Same contract as flow_field._batched_peaks (flow_field.py:205-275),
-  including its batch-coupled second-peak suppression.
+  including its batch-coupled second-peak suppression.  A surface that holds a
+  NaN has a NaN row, like the reference's; negative `min_distance` or
+  `peak_radius` raise ValueError.
   """
+  if not isinstance(min_distance, collections.abc.Sequence) and int(min_distance) < 0:
+    raise ValueError(f'min_distance must be >= 0, got {min_distance}')
+  radii = peak_radius if isinstance(peak_radius, collections.abc.Sequence) else (peak_radius,)
+  if any(int(r) < 0 for r in radii):
+    raise ValueError(f'peak_radius must be >= 0, got {peak_radius}')
   dev = _dev.device()
   surf = _dev.as_device_f32(img, dev, copy=False)
   dim = surf.ndim - 1
