@@ -37,7 +37,10 @@ extern "C" {
                                 6: SfmBandedDesc.host_halo / host_allgather / host_user;
                                 7: sfm_ndimage_warp; 8: SfmProfile.tiles_abandoned;
                                 9: SfmMaskIrregularDesc and SfmCleanFlowDesc carry
-                                   double thresholds */
+                                   double thresholds; sfm_map_shift, sfm_map_extents,
+                                   sfm_affine_map and sfm_warp_points were added
+                                   without a bump: new entry points only, no
+                                   existing struct or call changed */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -502,6 +505,110 @@ typedef struct SfmNdWarpDesc {
 } SfmNdWarpDesc;
 
 int sfm_ndimage_warp(const SfmNdWarpDesc* desc);
+
+/* ------------------------------------------------------------------------
+ * Map geometry: the one-pass helpers that the reference's renderers call
+ * around invert_map and the warps (sfm_mapgeom.hip).  Maps are [ncomp, z, y,
+ * x] with channels x, y[, z], float32 or float64 (`f64`).  Arithmetic is the
+ * reference's NumPy arithmetic: offsets are formed in double, added to the
+ * widened element, and the sum is narrowed once to the map's type.
+ * ---------------------------------------------------------------------- */
+#define SFM_SHIFT_TO_ABSOLUTE 0
+#define SFM_SHIFT_TO_RELATIVE 1
+
+/* map_utils.to_absolute / to_relative (map_utils.py:150-224):
+ * out[c] = T(double(in[c]) +/- (index_c * stride_c + start_c)), index_c the
+ * x / y / z node index for channel 0 / 1 / 2. */
+typedef struct SfmMapShiftDesc {
+  int32_t ncomp;                /* 2 or 3                                     */
+  int32_t f64;                  /* 1: maps hold doubles, 0: floats            */
+  int32_t direction;            /* SFM_SHIFT_*                                */
+  int32_t shape[3];             /* z, y, x                                    */
+  double stride[3];             /* z, y, x (entry 0 unused for ncomp 2)       */
+  double start[3];              /* z, y, x: box.start * stride in double, 0
+                                   without a box                              */
+  const void* coord_map;        /* device [ncomp, z, y, x]                    */
+  void* out;                    /* device, same shape; may equal coord_map    */
+  void* stream;
+} SfmMapShiftDesc;
+
+int sfm_map_shift(const SfmMapShiftDesc* desc);
+
+/* map_utils.outer_box / inner_box (map_utils.py:307-389): reductions over the
+ * ABSOLUTE map (rounded as sfm_map_shift rounds it), which is never stored.
+ *   OUTER  result[2c], result[2c + 1] = nanmin, nanmax of channel c; an
+ *          all-NaN channel gives +inf, -inf.
+ *   INNER  result[2a], result[2a + 1] = max over the lines along axis a of the
+ *          line's min, min over the lines of the line's max, of channel a
+ *          (a = 0: x, lines along x; 1: y; 2: z).  result[6] is non-zero when
+ *          the map holds a NaN; the other entries are then meaningless.
+ * result: 8 doubles on the device (values widened exactly from the map's
+ * type), written by the last launch; deterministic.  workspace: at least
+ * SFM_MAP_EXTENTS_WORKSPACE_BYTES. */
+#define SFM_EXTENTS_OUTER 0
+#define SFM_EXTENTS_INNER 1
+#define SFM_MAP_EXTENTS_WORKSPACE_BYTES (3 * 1024 * 4 * 8)
+
+typedef struct SfmMapExtentsDesc {
+  int32_t ncomp;                /* 2 or 3                                     */
+  int32_t f64;
+  int32_t mode;                 /* SFM_EXTENTS_*                              */
+  int32_t shape[3];             /* z, y, x                                    */
+  double stride[3];             /* z, y, x                                    */
+  double start[3];              /* z, y, x: box.start * stride                */
+  const void* coord_map;        /* device [ncomp, z, y, x], relative format   */
+  double* result;               /* device [8]                                 */
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+} SfmMapExtentsDesc;
+
+int sfm_map_extents(const SfmMapExtentsDesc* desc);
+
+/* map_utils.make_affine_map (map_utils.py:789-811):
+ * p = (x * stride_x + start_x, y * stride_y + start_y, z * stride_z + start_z),
+ * out[c] = ((m[c][0] p_x + m[c][1] p_y) + m[c][2] p_z) + m[c][3] - p_c, plain
+ * left-to-right double arithmetic. */
+typedef struct SfmAffineMapDesc {
+  int32_t shape[3];             /* z, y, x nodes (box.size reversed)          */
+  double stride[3];             /* z, y, x                                    */
+  double start[3];              /* z, y, x: box.start (NOT times stride)      */
+  double matrix[12];            /* row-major [3, 4], rows and columns x, y, z */
+  double* out;                  /* device [3, z, y, x]                        */
+  void* stream;
+} SfmAffineMapDesc;
+
+int sfm_affine_map(const SfmAffineMapDesc* desc);
+
+/* warp.warp_points (warp.py:541-605): every point reads the four map nodes
+ * around it in its section and combines them with bilinear weights in double
+ * (linear extrapolation outside the grid), like scipy's
+ * RegularGridInterpolator(bounds_error=False, fill_value=None) on the absolute
+ * map.  A node is T(double(T(double(m) + index * stride)) + origin); the grid
+ * coordinate of node j is (j + grid_start) * stride.  The result is narrowed to
+ * float and, for integer points, rounded half to even. */
+#define SFM_POINT_F32 0
+#define SFM_POINT_F64 1
+#define SFM_POINT_I32 2
+#define SFM_POINT_I64 3
+
+typedef struct SfmWarpPointsDesc {
+  int32_t f64;                  /* type of coord_map                          */
+  int32_t point_dtype;          /* SFM_POINT_* of points and out              */
+  int32_t shape[3];             /* z, y, x of coord_map; y, x >= 2            */
+  int64_t n;                    /* points                                     */
+  double stride;                /* > 0                                        */
+  double origin[2];             /* x, y: map_box.start * stride               */
+  int64_t grid_start[2];        /* x, y: map_box.start                        */
+  const void* coord_map;        /* device [2, z, y, x], relative format       */
+  const void* points;           /* device [n, 3], xyz                         */
+  const int32_t* section;       /* device [n]: section of every point, in
+                                   [0, z); other values give NaN / 0           */
+  void* out;                    /* device [n, 3]; columns x and y are written */
+  void* stream;
+} SfmWarpPointsDesc;
+
+int sfm_warp_points(const SfmWarpPointsDesc* desc);
 
 /* ------------------------------------------------------------------------
  * Dynamic-range mask of an overlap strip, the step in front of the

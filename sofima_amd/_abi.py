@@ -233,6 +233,72 @@ class SfmNdWarpDesc(C.Structure):
   ]
 
 
+SHIFT_TO_ABSOLUTE = 0
+SHIFT_TO_RELATIVE = 1
+EXTENTS_OUTER = 0
+EXTENTS_INNER = 1
+MAP_EXTENTS_WORKSPACE_BYTES = 3 * 1024 * 4 * 8
+POINT_F32, POINT_F64, POINT_I32, POINT_I64 = 0, 1, 2, 3
+
+
+class SfmMapShiftDesc(C.Structure):
+  _fields_ = [
+      ('ncomp', i32),
+      ('f64', i32),
+      ('direction', i32),
+      ('shape', i32 * 3),
+      ('stride', C.c_double * 3),
+      ('start', C.c_double * 3),
+      ('coord_map', C.c_void_p),
+      ('out', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
+class SfmMapExtentsDesc(C.Structure):
+  _fields_ = [
+      ('ncomp', i32),
+      ('f64', i32),
+      ('mode', i32),
+      ('shape', i32 * 3),
+      ('stride', C.c_double * 3),
+      ('start', C.c_double * 3),
+      ('coord_map', C.c_void_p),
+      ('result', C.c_void_p),
+      ('workspace', C.c_void_p),
+      ('workspace_bytes', C.c_size_t),
+      ('stream', C.c_void_p),
+  ]
+
+
+class SfmAffineMapDesc(C.Structure):
+  _fields_ = [
+      ('shape', i32 * 3),
+      ('stride', C.c_double * 3),
+      ('start', C.c_double * 3),
+      ('matrix', C.c_double * 12),
+      ('out', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
+class SfmWarpPointsDesc(C.Structure):
+  _fields_ = [
+      ('f64', i32),
+      ('point_dtype', i32),
+      ('shape', i32 * 3),
+      ('n', C.c_int64),
+      ('stride', C.c_double),
+      ('origin', C.c_double * 2),
+      ('grid_start', C.c_int64 * 2),
+      ('coord_map', C.c_void_p),
+      ('points', C.c_void_p),
+      ('section', C.c_void_p),
+      ('out', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmRangeMaskDesc(C.Structure):
   _fields_ = [
       ('dtype', i32),
@@ -403,6 +469,10 @@ SIGNATURES = {
     'sfm_flow_scatter': (C.c_int, [C.POINTER(SfmFlowScatterDesc)]),
     'sfm_warp_section': (C.c_int, [C.POINTER(SfmWarpDesc)]),
     'sfm_ndimage_warp': (C.c_int, [C.POINTER(SfmNdWarpDesc)]),
+    'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),
+    'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
+    'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),
+    'sfm_warp_points': (C.c_int, [C.POINTER(SfmWarpPointsDesc)]),
     'sfm_range_mask': (C.c_int, [C.POINTER(SfmRangeMaskDesc), C.c_void_p]),
     'sfm_target_mesh': (C.c_int, [C.POINTER(SfmTargetMeshDesc), C.c_void_p,
                                   C.c_void_p, C.c_void_p]),

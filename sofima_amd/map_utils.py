@@ -1,13 +1,19 @@
-"""Coordinate-map composition and inversion on MI355X.
+"""Coordinate-map composition, inversion and geometry helpers on MI355X.
 
 Drop-ins for `map_utils.compose_maps_fast` of the reference
-(map_utils.py:616-734), `map_utils.mask_irregular` (:737-786) and the 2-D
-branch of `map_utils.invert_map` (:392-463).  `invert_map` triangulates the
-deformed positions, so its Delaunay triangulation is unique and the device
-result has a parity contract.  `resample_map`, `compose_maps` and
-`fill_missing` triangulate the regular lattice, where every quad is
-co-circular and Qhull picks the diagonals arbitrarily; they stay host
-geometry and out of scope.
+(map_utils.py:616-734), `map_utils.mask_irregular` (:737-786), the 2-D
+branch of `map_utils.invert_map` (:392-463) and the helpers that the
+reference's renderers call around them: `to_absolute` / `to_relative`
+(:150-224), `outer_box` (:307-342), `inner_box` (:345-389, maps without NaN)
+and `make_affine_map` (:789-811).  The helpers are one pass over memory each
+and take and return `DeviceArray`s, so a map produced by `invert_map` or
+`compose_maps_fast` is shifted or measured without a host round trip.
+`invert_map` triangulates the deformed positions, so its Delaunay
+triangulation is unique and the device result has a parity contract.
+`resample_map`, `compose_maps` and `fill_missing` triangulate the regular
+lattice, where every quad is co-circular and Qhull picks the diagonals
+arbitrarily; they stay host geometry and out of scope (and with
+`fill_missing`, `inner_box` of a map that holds NaN).
 """
 from __future__ import annotations
 
@@ -213,4 +219,222 @@ def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
     why = ', '.join(r for bit, r in _INVMAP_REASONS if st[z] & bit)
     more = f' ({bad.size} slices refused: {bad.tolist()[:8]})' if bad.size > 1 else ''
     raise _abi.SofimaAmdError(f'invert_map: slice {z} refused: {why}{more}')
+  return DeviceArray(out)
+
+
+# -- geometry helpers: to_absolute / to_relative / outer_box / inner_box /
+# -- make_affine_map ------------------------------------------------------------
+
+
+def _box(box):
+  """(start xyz, size xyz) of a bounding box object or (start, size) pair."""
+  if hasattr(box, 'start') and hasattr(box, 'size'):
+    return np.asarray(box.start), np.asarray(box.size)
+  return np.asarray(box[0]), np.asarray(box[1])
+
+
+def _make_box(like, start, size):
+  """A box of the kind of `like`: its own type, or a (start, size) pair of int
+  arrays when `like` is a pair (the assignment into an int array truncates, as
+  the reference's `start[i] = ...` does)."""
+  if hasattr(like, 'start') and hasattr(like, 'size'):
+    return type(like)(start=start, size=size)
+  return np.array(start).astype(np.int64), np.array(size).astype(np.int64)
+
+
+def _device_map(coord_map, dev) -> torch.Tensor:
+  """[2 or 3, z, y, x] float32 / float64 contiguous device tensor; the dtype is
+  kept (other dtypes become float64, NumPy's result of adding float64 offsets)."""
+  if isinstance(coord_map, DeviceArray):
+    coord_map = coord_map.tensor
+  if isinstance(coord_map, torch.Tensor):
+    t = coord_map
+    if t.dtype not in (torch.float32, torch.float64):
+      t = t.to(torch.float64)
+    t = t.to(dev).contiguous()
+  else:
+    arr = np.asarray(coord_map)
+    if arr.dtype not in (np.float32, np.float64):
+      arr = arr.astype(np.float64)
+    t = _dev.upload(np.ascontiguousarray(arr), dev)
+  if t.ndim != 4 or t.shape[0] not in (2, 3):
+    raise ValueError(f'coord_map must be [2 or 3, z, y, x], got shape {tuple(t.shape)}')
+  if t.numel() == 0:
+    raise ValueError(f'empty coord_map: {tuple(t.shape)}')
+  return t
+
+
+def _zyx3(values, dim, fill):
+  """[z]yx values padded to 3 doubles (the z entry of 2-channel maps is `fill`)."""
+  return (C.c_double * 3)(*([fill] * (3 - dim) + [float(v) for v in values]))
+
+
+def _box_offsets(m, stride, box):
+  """(stride zyx, box.start * stride zyx) as the reference forms them."""
+  dim = m.shape[0]
+  stride = _as_vec(stride, dim)
+  start = [0.0] * dim
+  if box is not None:
+    b_start, b_size = _box(box)
+    if not np.all(tuple(m.shape)[-dim:][::-1] == b_size[:dim]):
+      raise ValueError(
+          f'box shape ({b_size}) mismatch with coord map ({tuple(m.shape)})')
+    # float64 like NumPy: int64 start times a Python / NumPy scalar stride
+    start = [float(np.float64(s) * np.float64(st))
+             for s, st in zip(b_start[:dim][::-1], stride)]
+  return stride, start
+
+
+def _shift(coord_map, stride, box, direction) -> DeviceArray:
+  dev = _dev.device()
+  m = _device_map(coord_map, dev)
+  dim = m.shape[0]
+  stride, start = _box_offsets(m, stride, box)
+  out = torch.empty_like(m)
+  d = _abi.SfmMapShiftDesc()
+  d.ncomp = dim
+  d.f64 = int(m.dtype == torch.float64)
+  d.direction = direction
+  d.shape = (C.c_int32 * 3)(*m.shape[1:])
+  d.stride = _zyx3(stride, dim, 1.0)
+  d.start = _zyx3(start, dim, 0.0)
+  d.coord_map = m.data_ptr()
+  d.out = out.data_ptr()
+  d.stream = _dev.stream_ptr()
+  _abi.check(_abi.load().sfm_map_shift(C.byref(d)))
+  return DeviceArray(out)
+
+
+def to_absolute(coord_map, stride, box=None) -> DeviceArray:
+  """Converts a [2 or 3, z, y, x] map from relative to absolute representation.
+
+  Same contract as the reference (map_utils.py:150-185): `stride` is a scalar
+  or a [z]yx sequence; `box` (`.start` / `.size` in xyz, or a (start, size)
+  pair) places the origin, and its size must agree with the map.  The map
+  (NumPy, torch or DeviceArray, float32 or float64) is never written; the
+  result has its dtype.  Arithmetic is NumPy's in-place `+=` of a float64
+  offset array: index * stride (+ start * stride) is formed in double, added to
+  the widened element and the sum narrowed once.
+  """
+  return _shift(coord_map, stride, box, _abi.SHIFT_TO_ABSOLUTE)
+
+
+def to_relative(coord_map, stride, box=None) -> DeviceArray:
+  """Converts a [2 or 3, z, y, x] map from absolute to relative representation
+  (map_utils.py:188-224); the inverse bookkeeping of `to_absolute`, with the
+  same argument meaning and rounding."""
+  return _shift(coord_map, stride, box, _abi.SHIFT_TO_RELATIVE)
+
+
+def _extents(coord_map, stride, box, mode):
+  """The 8 doubles of sfm_map_extents (one host sync) and the map's NumPy dtype."""
+  dev = _dev.device()
+  m = _device_map(coord_map, dev)
+  dim = m.shape[0]
+  stride, start = _box_offsets(m, stride, box)
+  result = torch.empty(8, dtype=torch.float64, device=dev)
+  ws = _dev.workspace(_abi.MAP_EXTENTS_WORKSPACE_BYTES, dev)
+  d = _abi.SfmMapExtentsDesc()
+  d.ncomp = dim
+  d.f64 = int(m.dtype == torch.float64)
+  d.mode = mode
+  d.shape = (C.c_int32 * 3)(*m.shape[1:])
+  d.stride = _zyx3(stride, dim, 1.0)
+  d.start = _zyx3(start, dim, 0.0)
+  d.coord_map = m.data_ptr()
+  d.result = result.data_ptr()
+  d.workspace = ws.data_ptr()
+  d.workspace_bytes = ws.numel()
+  d.stream = _dev.stream_ptr()
+  _abi.check(_abi.load().sfm_map_extents(C.byref(d)))
+  dtype = np.float64 if m.dtype == torch.float64 else np.float32
+  return result.cpu().numpy(), dtype, dim, stride
+
+
+def outer_box(coord_map, box, stride, target_len=None):
+  """Returns a bounding box covering all target nodes (map_utils.py:307-342).
+
+  `coord_map` is in relative format, `box` the box it was extracted from,
+  `target_len` the node spacing of the output box ([z]yx or a scalar, defaults
+  to `stride`).  The device reduces nanmin / nanmax per channel of the absolute
+  map in one pass without storing it; the reference's integer expressions are
+  applied to those scalars on the host.  An all-NaN channel raises ValueError,
+  as `int(nan)` does in the reference.  The box is of the type of `box`.
+  """
+  res, dtype, dim, stride = _extents(coord_map, stride, box, _abi.EXTENTS_OUTER)
+  target_len_xyz = _as_vec(target_len if target_len is not None else stride, dim)[::-1]
+  b_start, b_size = _box(box)
+  start = np.array(b_start).copy()
+  size = np.array(b_size).copy()
+  for i, tl in enumerate(target_len_xyz):
+    if res[2 * i] == np.inf and res[2 * i + 1] == -np.inf:   # no finite or infinite value
+      x_min = x_max = dtype(np.nan)
+    else:
+      x_min, x_max = dtype(res[2 * i]), dtype(res[2 * i + 1])
+    x_min = int(x_min) // tl
+    start[i] = x_min
+    size[i] = -(int(-x_max) // tl) - x_min + 1
+  return _make_box(box, start, size)
+
+
+def inner_box(coord_map, box, stride):
+  """Returns a box within which all nodes are mapped to by the map
+  (map_utils.py:345-389), for maps WITHOUT NaN.
+
+  The reference first extrapolates invalid entries with `fill_missing`, which
+  returns a NaN-free map unchanged; `fill_missing` has no parity contract (see
+  the module docstring), so a map that holds a NaN raises NotImplementedError.
+  The device returns the max of the per-line minima and the min of the per-line
+  maxima of the absolute map along x, y[, z] in the map's dtype; the
+  reference's `//` expressions are applied to NumPy scalars of that dtype.
+  """
+  res, dtype, dim, stride = _extents(coord_map, stride, box, _abi.EXTENTS_INNER)
+  if res[6] != 0:
+    raise NotImplementedError(
+        'inner_box: the map holds NaN; the reference extrapolates them with '
+        'fill_missing, which is not on the device')
+  x0, x1, y0, y1, z0, z1 = (dtype(v) for v in res[:6])
+  b_start, b_size = _box(box)
+
+  x0 = int(-(-x0 // stride[-1]))
+  y0 = int(-(-y0 // stride[-2]))
+  x1 = x1 // stride[-1]
+  y1 = y1 // stride[-2]
+
+  if dim == 2:
+    return _make_box(box, (x0, y0, b_start[2]),
+                     (x1 - x0 + 1, y1 - y0 + 1, b_size[2]))
+
+  z0 = int(-(-z0 // stride[0]))
+  z1 = z1 // stride[0]
+  return _make_box(box, (x0, y0, z0), (x1 - x0 + 1, y1 - y0 + 1, z1 - z0 + 1))
+
+
+def make_affine_map(matrix, box, stride) -> DeviceArray:
+  """Builds a [3, z, y, x] float64 coordinate map for an affine transform
+  (map_utils.py:789-811): `matrix` is [3, 4] in the format of
+  ndimage.affine_transform with xyz rows and columns, `box` the box to
+  generate the map for, `stride` zyx or a scalar.  Node positions are
+  index * stride + box.start; the map is matrix[:, :3] @ p + matrix[:, 3] - p in
+  plain left-to-right float64 (the reference's np.dot may fuse or reorder the
+  three products: the results agree to a few ulp of the largest term).
+  """
+  matrix = np.asarray(matrix, dtype=np.float64)
+  if matrix.shape != (3, 4):
+    raise ValueError(f'matrix must be [3, 4], got {matrix.shape}')
+  b_start, b_size = _box(box)
+  shape = tuple(int(v) for v in b_size[::-1])
+  if len(shape) != 3 or min(shape) < 1:
+    raise ValueError(f'box size must be 3 positive entries, got {b_size}')
+  stride = _as_vec(stride, 3)
+  dev = _dev.device()
+  out = torch.empty((3,) + shape, dtype=torch.float64, device=dev)
+  d = _abi.SfmAffineMapDesc()
+  d.shape = (C.c_int32 * 3)(*shape)
+  d.stride = _zyx3(stride, 3, 1.0)
+  d.start = _zyx3(b_start[:3][::-1], 3, 0.0)
+  d.matrix = (C.c_double * 12)(*matrix.ravel())
+  d.out = out.data_ptr()
+  d.stream = _dev.stream_ptr()
+  _abi.check(_abi.load().sfm_affine_map(C.byref(d)))
   return DeviceArray(out)

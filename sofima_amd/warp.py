@@ -20,7 +20,10 @@ real OpenCV build (which tap takes a table's rounding remainder).
 `ndimage_warp` (warp.py:189-335), the SciPy-only rendering path, is built as
 well and IS pinned: the reference function runs through the golden shim and
 the kernel reproduces its output bit for bit (tests/golden/ndimage_warp.npz).
-render_tiles and warp_points are host-side utilities and out of scope.
+`warp_points` (warp.py:541-605) maps point sets through a coordinate map: one
+kernel, every point reads its four map nodes directly, pinned against the
+reference function through the golden shim (tests/golden/mapgeom.npz).
+render_tiles has no parity contract and stays out of scope.
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ import torch
 
 from . import _abi
 from . import _dev
+from . import map_utils
 
 _INTER = {'nearest': 0, 'linear': 1, 'cubic': 2, 'lanczos': 3}
 _TAB = 32            # INTER_TAB_SIZE
@@ -329,3 +333,93 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
   if image.dtype == np.uint16:
     warped = warped.view(np.uint16)
   return warped.astype(image.dtype)
+
+
+_POINT_DTYPES = {np.dtype(np.float32): _abi.POINT_F32, np.dtype(np.float64): _abi.POINT_F64,
+                 np.dtype(np.int32): _abi.POINT_I32, np.dtype(np.int64): _abi.POINT_I64}
+
+
+def warp_points(points: np.ndarray, coord_map, map_box, stride: float) -> np.ndarray:
+  """Warps a collection of points (warp.py:541-605).
+
+  points: [n, 3] in xyz order (float32, float64, int32 or int64; other integer
+  dtypes are computed as int64 and cast back); coord_map: [2, z, y, x]
+  relative map (NumPy, torch or DeviceArray, float32 or float64); map_box: the
+  map's box (`.start` / `.size` in xyz, or a (start, size) pair); stride: map
+  stride in pixels, a scalar.  Returns a NumPy array of the points' dtype: z
+  unchanged, x and y mapped; integer dtypes are rounded half to even.
+
+  Only in-plane warping, like the reference.  A point's section is
+  `int(z - map_box.start[2])`, indexed like NumPy (negative values wrap,
+  anything outside [-nz, nz) raises IndexError, checked before the launch).
+  Each of the four nodes around the point is the absolute map value, rounded
+  twice in the map's dtype as the reference's `to_absolute` and `+= origin` do;
+  they are combined with bilinear weights in float64 in the order of SciPy's
+  RegularGridInterpolator (linear extrapolation from the edge cell outside the
+  grid) and narrowed to float32.  Nothing per section is materialised.
+  """
+  points = np.array(points)
+  assert points.ndim == 2
+  assert points.shape[1] == 3
+  dev = _dev.device()
+  m = map_utils._device_map(coord_map, dev)
+  assert m.shape[0] == 2
+  nz, ny, nx = (int(v) for v in m.shape[1:])
+  if ny < 2 or nx < 2:
+    raise ValueError(
+        f'There are {min(ny, nx)} points and at least 2 are required in '
+        f'dimension {0 if ny < 2 else 1}')
+  stride = float(stride)
+  if not (np.isfinite(stride) and stride > 0):
+    raise ValueError('The points in dimension 0 must be strictly ascending')
+  ret = points.copy()
+  n = points.shape[0]
+  if n == 0:
+    return ret
+  map_start, _ = _box(map_box)
+  map_start = [int(v) for v in map_start[:3]]
+
+  dtype = points.dtype
+  if dtype not in _POINT_DTYPES:
+    if not np.issubdtype(dtype, np.integer):
+      raise NotImplementedError(f'warp_points: {dtype} points')
+    points = points.astype(np.int64)
+  # section of every point: int(z - start) of a NumPy scalar and an int64 start
+  # (float32 z is widened to float64 first), then Python indexing
+  z = points[:, 2]
+  if np.issubdtype(z.dtype, np.integer):
+    z_rel = z.astype(np.int64) - map_start[2]
+  else:
+    dz = z.astype(np.float64) - np.float64(map_start[2])
+    if not np.all(np.isfinite(dz)):
+      raise ValueError('cannot convert float NaN or infinity to integer')
+    outside = np.abs(dz) >= 2.0**31
+    if outside.any():
+      raise IndexError(f'index {int(dz[outside][0])} is out of bounds for axis 1 with size {nz}')
+    z_rel = np.trunc(dz).astype(np.int64)
+  bad = (z_rel < -nz) | (z_rel >= nz)
+  if bad.any():
+    raise IndexError(
+        f'index {int(z_rel[bad][0])} is out of bounds for axis 1 with size {nz}')
+  z_rel = np.where(z_rel < 0, z_rel + nz, z_rel).astype(np.int32)
+
+  pts_t = _dev.upload(np.ascontiguousarray(points), dev)
+  sec_t = _dev.upload(np.ascontiguousarray(z_rel), dev)
+  out_t = pts_t.clone()
+  d = _abi.SfmWarpPointsDesc()
+  d.f64 = int(m.dtype == torch.float64)
+  d.point_dtype = _POINT_DTYPES[points.dtype]
+  d.shape = (C.c_int32 * 3)(nz, ny, nx)
+  d.n = n
+  d.stride = stride
+  d.origin = (C.c_double * 2)(float(np.float64(map_start[0]) * stride),
+                              float(np.float64(map_start[1]) * stride))
+  d.grid_start = (C.c_int64 * 2)(map_start[0], map_start[1])
+  d.coord_map = m.data_ptr()
+  d.points = pts_t.data_ptr()
+  d.section = sec_t.data_ptr()
+  d.out = out_t.data_ptr()
+  d.stream = _dev.stream_ptr()
+  _abi.check(_abi.load().sfm_warp_points(C.byref(d)))
+  ret[...] = out_t.cpu().numpy().astype(dtype, copy=False)
+  return ret
