@@ -410,7 +410,8 @@ typedef struct SfmInvertMapDesc {
 /* Host arithmetic only (callable without a GPU); 0 for a NULL descriptor or
  * an empty shape. */
 size_t sfm_invert_map_workspace_bytes(const SfmInvertMapDesc* desc);
-/* out: device double [2, z, dst y, dst x]; must not overlap coord_map.
+/* out: device double [2, z, dst y, dst x]; must not overlap coord_map; may
+ * be NULL when the output lattice is empty (status is still written).
  * Asynchronous: read status after the stream has finished. */
 int sfm_invert_map(const SfmInvertMapDesc* desc, double* out);
 

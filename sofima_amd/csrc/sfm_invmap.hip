@@ -950,7 +950,9 @@ extern "C" size_t sfm_invert_map_workspace_bytes(const SfmInvertMapDesc* d) {
 }
 
 extern "C" int sfm_invert_map(const SfmInvertMapDesc* d, double* out) {
-  if (!d || !d->coord_map || !d->status || !out)
+  // an empty dst box has no output to point at
+  if (!d || !d->coord_map || !d->status ||
+      (!out && d->dst_shape[0] > 0 && d->dst_shape[1] > 0))
     return sfm::fail(SFM_ERR_INVALID, "invert_map: NULL argument");
   for (int i = 0; i < 3; ++i)
     if (d->shape[i] < 1) return sfm::fail(SFM_ERR_INVALID, "invert_map: bad shape");

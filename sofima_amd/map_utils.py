@@ -161,13 +161,17 @@ def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
   (both channels finite) are triangulated at their absolute positions
   (Delaunay) and the source lattice coordinates are interpolated linearly at
   the dst lattice; queries outside the convex hull and slices with fewer than
-  3 valid or only collinear nodes are NaN.  Computed in float64 on the device;
-  returns a float64 [2, z, dst y, dst x] DeviceArray in relative format.
+  3 valid or only collinear nodes are NaN (a slice that has a quad of four
+  valid nodes on one line or at one point is refused as degenerate instead).
+  A dst box of size 0 on an axis gives an empty result.  Computed in float64
+  on the device; returns a float64 [2, z, dst y, dst x] DeviceArray in
+  relative format.
 
   The triangulation is verified on the device (one host sync reads the
   per-slice status).  A slice that cannot be answered exactly -- folded, more
   than 7936 boundary nodes, or a lattice part that is not Delaunay -- raises
-  SofimaAmdError naming the slice and the reason; it is never answered wrongly.
+  SofimaAmdError naming the first such slice and its reason, the refused
+  slices, and the reason of each that differs; it is never answered wrongly.
   """
   shape = tuple(int(v) for v in np.shape(coord_map)) if not isinstance(
       coord_map, (torch.Tensor, DeviceArray)) else tuple(coord_map.shape)
@@ -215,10 +219,16 @@ def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
   st = status.cpu().numpy()
   bad = np.flatnonzero(st)
   if bad.size:
+    def why(k):
+      return ', '.join(r for bit, r in _INVMAP_REASONS if st[k] & bit)
+
     z = int(bad[0])
-    why = ', '.join(r for bit, r in _INVMAP_REASONS if st[z] & bit)
-    more = f' ({bad.size} slices refused: {bad.tolist()[:8]})' if bad.size > 1 else ''
-    raise _abi.SofimaAmdError(f'invert_map: slice {z} refused: {why}{more}')
+    more = ''
+    if bad.size > 1:
+      # the listed slices that were refused for another reason than the first
+      other = ''.join(f'; slice {int(k)}: {why(k)}' for k in bad[1:8] if st[k] != st[z])
+      more = f' ({bad.size} slices refused: {bad.tolist()[:8]}{other})'
+    raise _abi.SofimaAmdError(f'invert_map: slice {z} refused: {why(z)}{more}')
   return DeviceArray(out)
 
 

@@ -105,18 +105,26 @@ def _incircle_norm(a, b, c, d):
 def check_contract(coord_map, src_box, dst_box, stride, got, want, tol=1e-6):
   """Asserts the parity contract; returns the number of nodes accepted by the
   diagonal exception."""
+  return check_contract_counts(coord_map, src_box, dst_box, stride, got, want, tol)[0]
+
+
+def check_contract_counts(coord_map, src_box, dst_box, stride, got, want, tol=1e-6):
+  """Asserts the parity contract; returns (nodes accepted by the diagonal
+  exception, nodes whose NaN masks differ on the hull)."""
   got = np.asarray(got, np.float64)
   want = np.asarray(want, np.float64)
   assert got.shape == want.shape, (got.shape, want.shape)
   pos, vals, qry, (sy, sx) = slice_geometry(coord_map, src_box, dst_box, stride)
   h, w = pos.shape[2:]
   diag = 0
+  mismatches = 0
   yy, xx = np.mgrid[:got.shape[2], :got.shape[3]]
   for k in range(got.shape[1]):
     gn = np.isnan(got[0, k]) | np.isnan(got[1, k])
     wn = np.isnan(want[0, k]) | np.isnan(want[1, k])
     assert np.array_equal(np.isnan(got[0, k]), np.isnan(got[1, k]))
     mism = gn != wn
+    mismatches += int(mism.sum())
     valid = np.all(np.isfinite(pos[:, k]), axis=0)
     if mism.any():
       pts = np.stack([pos[0, k][valid], pos[1, k][valid]], axis=1)
@@ -152,4 +160,4 @@ def check_contract(coord_map, src_box, dst_box, stride, got, want, tol=1e-6):
       assert ok, (f'slice {k}, node (y={v}, x={u}): device {got[:, k, v, u]}, '
                   f'host {want[:, k, v, u]}')
       diag += 1
-  return diag
+  return diag, mismatches

@@ -33,7 +33,9 @@ def test_golden_cases_meet_the_contract(case):
   got = np.asarray(got)
   assert got.dtype == np.float64 and got.shape == want.shape
   diag = ims.check_contract(cm, src, dst, stride, got, want)
-  print(f'{name}: {diag} nodes by the diagonal exception')
+  # the SciPy statement needs no exception against these outputs either
+  # (tests/test_invert_map_cases.py::test_golden_cases_need_no_exception_on_the_host)
+  assert diag == 0, f'{name}: {diag} nodes by the diagonal exception'
 
 
 def test_reference_kat():
@@ -81,7 +83,7 @@ def test_scipy_fuzz(seed, shape, holes):
   got = np.asarray(map_utils.invert_map(cm.astype(np.float32), src, dst, 40))
   want = ims.invert_restated(cm.astype(np.float32), src, dst, 40)
   diag = ims.check_contract(cm.astype(np.float32), src, dst, 40, got, want)
-  print(f'seed {seed}: {diag} nodes by the diagonal exception')
+  assert diag == 0, f'seed {seed}: {diag} nodes by the diagonal exception'
 
 
 def _folded():
