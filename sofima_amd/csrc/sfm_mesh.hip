@@ -24,6 +24,21 @@
 //                 per-block partials -> global
 //   finish:       the pending gate / drift / scalar update of the last step,
 //                 then e_kin and v_max.
+//
+// Single definitions, called by every integrator (each follows the reference's f32
+// operation order, so there is one place to change it):
+//   fire_next / scalars_from_sums / no_pending_update   the FIRE scalar update
+//   node_force_tile2d<TW>                               2-D force from an LDS tile
+//   StepLaw, step_law, fire_mix<C>, node_update<C>      velocity Verlet + FIRE mixing
+//   TileFrame<T>, persist_write_back<T>                 frame of the persistent kernels
+// Kept apart on purpose: mesh_persist2d_spec_kernel<16> evaluates every spring once
+// (another algorithm than the eight-term sum); integrate_shared2d_kernel and
+// integrate_march3d_kernel keep their per-component loops, the march kernel also its
+// own dt / alpha / cap choice and mixing loop (with the shared forms they spill more
+// VGPRs); the persistent kernels ASSIGN their per-node sums (part[1] = x0) where
+// the others accumulate from zero -- the two differ for -0.0f; and each persistent
+// kernel loads its initial state itself (eight lines; a shared load was a judgement
+// call against it: it only reshuffled mesh_persist2d_spec_kernel<16>'s registers).
 #include "sfm_common.h"
 
 #include <cmath>
@@ -555,13 +570,12 @@ __device__ void block_sum(float* vals, int nv, float* lds) {
   __syncthreads();
 }
 
-// Advances the FIRE scalars from the summed partials of the previous step
-// (mesh.py:455-497).
-__device__ void scalars_from_sums(const Scalars& in, const float* acc,
-                                  const MeshParams& p, Scalars* out) {
-  const float power = acc[0];
+// The FIRE scalar update for a known sign of the power (mesh.py:459-490): n_pos,
+// dt, alpha, cap and the velocity gate.  The only definition; the drift means are
+// scalars_from_sums'.
+__device__ __forceinline__ Scalars fire_next(const Scalars& in, bool downhill,
+                                             const MeshParams& p) {
   Scalars s = in;
-  const bool downhill = power >= 0.f;
   s.n_pos = downhill ? in.n_pos + 1 : 0;
   if (downhill) {
     if (s.n_pos > p.n_min) {
@@ -575,11 +589,28 @@ __device__ void scalars_from_sums(const Scalars& in, const float* acc,
   }
   s.cap = fminf(s.cap, p.final_cap);
   s.gate = downhill ? 1.f : 0.f;
+  return s;
+}
+
+// Advances the FIRE scalars from the summed partials of the previous step
+// (mesh.py:455-497): fire_next for the sign of the power, plus the drift means.
+__device__ void scalars_from_sums(const Scalars& in, const float* acc,
+                                  const MeshParams& p, Scalars* out) {
+  Scalars s = fire_next(in, acc[0] >= 0.f, p);
   for (int c = 0; c < 3; ++c) {
     s.mx[c] = p.remove_drift ? acc[1 + c] / p.n_f : 0.f;
     s.mv[c] = p.remove_drift ? (acc[4 + c] / p.n_f) * s.gate : 0.f;
   }
   *out = s;
+}
+
+// The scalars of a step that has no pending update behind it (the first step of a
+// chunk, or no FIRE at all): `dt`, the gate open, nothing to remove.
+__device__ __forceinline__ Scalars no_pending_update(Scalars s, float dt) {
+  s.dt = dt;
+  s.gate = 1.f;
+  for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+  return s;
 }
 
 // Reduces the partials of the previous step and advances the FIRE scalars.
@@ -593,6 +624,76 @@ __device__ void update_scalars(const Scalars& in, const float* partials,
     for (int i = 0; i < 7; ++i) acc[i] = acc[i] + partials[r * kNP + i];
   block_sum(acc, 7, lds);
   scalars_from_sums(in, acc, p, out);
+}
+
+// The per-node step law (mesh.py:432-452), the only definition: damped velocity
+// Verlet v' = fact0 * (v * fact1 + hdt * (a + a')), then FIRE's velocity mixing.
+// dt, alpha, cap: the FIRE scalars of the step, or the fixed values without FIRE.
+// step_law(dt, alpha, cap, gamma) is the primitive; step_law(p, scalars, fixed_cap)
+// makes the FIRE / fixed choice in front of it.  The primitive is called directly
+// where that choice is already made: integrate_shared2d_kernel (its Scalars hold
+// the fixed values without FIRE), mesh_persist2d_spec_kernel (FIRE only) and
+// integrate_march3d_kernel (its own choice, see there).
+struct StepLaw {
+  float dt, alpha, cap;
+  float fact0, fact1, hdt;
+};
+
+__device__ __forceinline__ StepLaw step_law(float dt, float alpha, float cap, float gamma) {
+  StepLaw w;
+  w.dt = dt;
+  w.alpha = alpha;
+  w.cap = cap;
+  const float hdtg = (0.5f * dt) * gamma;
+  w.fact0 = 1.0f / (1.0f + hdtg);
+  w.fact1 = 1.0f - hdtg;
+  w.hdt = 0.5f * dt;
+  return w;
+}
+
+__device__ __forceinline__ StepLaw step_law(const MeshParams& p, const Scalars& s,
+                                            float fixed_cap) {
+  return p.fire ? step_law(s.dt, s.alpha, s.cap, p.gamma)
+                : step_law(p.vv_dt, 0.f, fixed_cap, p.gamma);
+}
+
+// vn += alpha * (f / |f| * |vn| - vn); a2, v2: the squared norms of f and vn.
+template <int C>
+__device__ __forceinline__ void fire_mix(const float* f, float* vn, float a2, float v2,
+                                         float alpha) {
+  const float a_norm = sqrtf(a2) + 1e-6f;
+  const float v_norm = sqrtf(v2);
+#pragma unroll
+  for (int c = 0; c < C; ++c) vn[c] = vn[c] + alpha * (f[c] / a_norm * v_norm - vn[c]);
+}
+
+// One node's update from operands in registers: the pull towards `pv` joins the
+// spring force f (which becomes the new a), vn is the new velocity; an `own` node
+// adds its terms to the caller's partial sums (power, sum x, sum v), component by
+// component.
+template <int C>
+__device__ __forceinline__ void node_update(const MeshParams& p, const StepLaw& w,
+                                            const float* xv, const float* pv,
+                                            const float* v_old, const float* a_old, bool own,
+                                            float* f, float* vn, float* part) {
+  float a2 = 0.f, v2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    if (p.has_prev) f[c] = f[c] + prev_pull(xv[c], pv[c], p.neg_k0, w.cap);
+    vn[c] = w.fact0 * (v_old[c] * w.fact1 + w.hdt * (a_old[c] + f[c]));
+    a2 = a2 + f[c] * f[c];
+    v2 = v2 + vn[c] * vn[c];
+    if (p.fire && own) {
+      part[0] = part[0] + f[c] * vn[c];
+      part[1 + c] = part[1 + c] + xv[c];
+    }
+  }
+  if (p.fire) {
+    fire_mix<C>(f, vn, a2, v2, w.alpha);
+    if (own)
+#pragma unroll
+      for (int c = 0; c < C; ++c) part[4 + c] = part[4 + c] + vn[c];
+  }
 }
 
 // x += dt v + dt^2/2 a, after applying the pending gate / drift of the
@@ -612,15 +713,11 @@ advance_kernel(float* __restrict__ x, float* __restrict__ v,
     } else if (pending == 2) {
       s = *scal_in;  // reduced by the last workgroup of the tiled integrator
     } else {
-      s = *scal_in;
-      s.gate = 1.f;
-      for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+      s = no_pending_update(*scal_in, scal_in->dt);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *scal_out = s;
   } else {
-    s.dt = p.vv_dt;
-    s.gate = 1.f;
-    for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+    s = no_pending_update(Scalars(), p.vv_dt);
   }
   const float dt = s.dt;
   const float c2 = 0.5f * (dt * dt);
@@ -657,20 +754,7 @@ integrate_kernel(const float* __restrict__ x, float* __restrict__ v,
                  MeshParams p, const Scalars* __restrict__ scal,
                  float fixed_cap, float* __restrict__ partials) {
   __shared__ float lds[kNP * kBlock];
-  float dt, alpha, cap;
-  if (p.fire) {
-    dt = scal->dt;
-    alpha = scal->alpha;
-    cap = scal->cap;
-  } else {
-    dt = p.vv_dt;
-    alpha = 0.f;
-    cap = fixed_cap;
-  }
-  const float hdtg = (0.5f * dt) * p.gamma;
-  const float fact0 = 1.0f / (1.0f + hdtg);
-  const float fact1 = 1.0f - hdtg;
-  const float hdt = 0.5f * dt;
+  const StepLaw w = step_law(p, *scal, fixed_cap);
   float part[kNP];
   for (int i = 0; i < kNP; ++i) part[i] = 0.f;
   for (long long n = blockIdx.x * (long long)kBlock + threadIdx.x; n < p.N;
@@ -681,32 +765,20 @@ integrate_kernel(const float* __restrict__ x, float* __restrict__ v,
     // the owner's at the next exchange) but do not count in the sums
     const int yrow = static_cast<int>((n / p.X) % p.Y);
     const bool own = yrow >= p.own_y0 && yrow < p.own_y1;
-    float a2 = 0.f, v2 = 0.f;
+    float xv[C], pv[C], v_old[C], a_old[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      const float xv = x[c * p.N + n];
-      if (p.has_prev) f[c] = f[c] + prev_pull(xv, prev[c * p.N + n], p.neg_k0, cap);
-      const float a_old = a[c * p.N + n];
-      vn[c] = fact0 * (v[c * p.N + n] * fact1 + hdt * (a_old + f[c]));
+      xv[c] = x[c * p.N + n];
+      pv[c] = p.has_prev ? prev[c * p.N + n] : 0.f;
+      v_old[c] = v[c * p.N + n];
+      a_old[c] = a[c * p.N + n];
+    }
+    node_update<C>(p, w, xv, pv, v_old, a_old, own, f, vn, part);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
       a[c * p.N + n] = f[c];
-      a2 = a2 + f[c] * f[c];
-      v2 = v2 + vn[c] * vn[c];
-      if (p.fire && own) {
-        part[0] = part[0] + f[c] * vn[c];
-        part[1 + c] = part[1 + c] + xv;
-      }
+      v[c * p.N + n] = vn[c];
     }
-    if (p.fire) {
-      const float a_norm = sqrtf(a2) + 1e-6f;
-      const float v_norm = sqrtf(v2);
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        vn[c] = vn[c] + alpha * (f[c] / a_norm * v_norm - vn[c]);
-        if (own) part[4 + c] = part[4 + c] + vn[c];
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) v[c * p.N + n] = vn[c];
   }
   if (p.fire) {
     block_sum(part, 7, lds);
@@ -842,6 +914,10 @@ integrate_march3d_kernel(const float* __restrict__ x, float* __restrict__ v,
   float* P = march_lds;           // [7][3][T]
   float* U = march_lds + 21 * T;  // [5][3][T]
   const int tid = threadIdx.x;
+  // (This kernel sits at the spill edge: with step_law(p, *scal, fixed_cap), fire_mix
+  // or node_update every instance spills more VGPRs -- scratch 16 -> 24 bytes at
+  // T = 256 with fire_mix alone, 16 -> 116 with node_update -- so it keeps its own
+  // choice of dt / alpha / cap and its per-component loop.)
   float dt, alpha, cap;
   if (p.fire) {
     dt = scal->dt;
@@ -852,10 +928,7 @@ integrate_march3d_kernel(const float* __restrict__ x, float* __restrict__ v,
     alpha = 0.f;
     cap = fixed_cap;
   }
-  const float hdtg = (0.5f * dt) * p.gamma;
-  const float fact0 = 1.0f / (1.0f + hdtg);
-  const float fact1 = 1.0f - hdtg;
-  const float hdt = 0.5f * dt;
+  const StepLaw w = step_law(dt, alpha, cap, p.gamma);
   const DefLinks3 dl(p);
   const int W = g.txh;
   const int tx = tid % W, ty = tid / W;
@@ -1003,9 +1076,9 @@ integrate_march3d_kernel(const float* __restrict__ x, float* __restrict__ v,
             float f = acc[c];
             // one base pointer per array, the component in the 32-bit offset
             const unsigned nbc = nb + c * Nb;
-            if (p.has_prev) f = f + prev_pull(xv, ld_b(prev, nbc), p.neg_k0, cap);
+            if (p.has_prev) f = f + prev_pull(xv, ld_b(prev, nbc), p.neg_k0, w.cap);
             const float a_old = ld_b(a, nbc);
-            vn[c] = fact0 * (ld_b(v, nbc) * fact1 + hdt * (a_old + f));
+            vn[c] = w.fact0 * (ld_b(v, nbc) * w.fact1 + w.hdt * (a_old + f));
             *reinterpret_cast<float*>(reinterpret_cast<char*>(a) + nbc) = f;
             acc[c] = f;
             a2 = a2 + f * f;
@@ -1020,7 +1093,7 @@ integrate_march3d_kernel(const float* __restrict__ x, float* __restrict__ v,
             const float v_norm = sqrtf(v2);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-              vn[c] = vn[c] + alpha * (acc[c] / a_norm * v_norm - vn[c]);
+              vn[c] = vn[c] + w.alpha * (acc[c] / a_norm * v_norm - vn[c]);
               if (own) part[4 + c] = part[4 + c] + vn[c];
             }
           }
@@ -1084,13 +1157,10 @@ mesh_small_kernel(float* x, float* v, float* a, const float* prev, MeshParams p,
         scalars_from_sums(s, acc, p, &sn);
         s = sn;
       } else {
-        s.gate = 1.f;
-        for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+        s = no_pending_update(s, s.dt);
       }
     } else {
-      s.dt = p.vv_dt;
-      s.gate = 1.f;
-      for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+      s = no_pending_update(s, p.vv_dt);
     }
     const float dt = s.dt;
     const float c2 = 0.5f * (dt * dt);
@@ -1112,48 +1182,25 @@ mesh_small_kernel(float* x, float* v, float* a, const float* prev, MeshParams p,
     }
     __syncthreads();  // every position of this step is visible
     // -- integrate_kernel --
-    float alpha, cap;
-    if (p.fire) {
-      alpha = s.alpha;
-      cap = s.cap;
-    } else {
-      alpha = 0.f;
-      cap = fixed_cap;
-    }
-    const float hdtg = (0.5f * dt) * p.gamma;
-    const float fact0 = 1.0f / (1.0f + hdtg);
-    const float fact1 = 1.0f - hdtg;
-    const float hdt = 0.5f * dt;
+    const StepLaw w = step_law(p, s, fixed_cap);
     for (int i = 0; i < kNP; ++i) part[i] = 0.f;
     if (live) {
       float f[C], vn[C];
       node_force<C>(x, p, n, f);
-      float a2 = 0.f, v2 = 0.f;
+      float xv[C], pv[C], v_old[C], a_old[C];
 #pragma unroll
       for (int c = 0; c < C; ++c) {
-        const float xv = x[c * p.N + n];
-        if (p.has_prev) f[c] = f[c] + prev_pull(xv, prev[c * p.N + n], p.neg_k0, cap);
-        const float a_old = a[c * p.N + n];
-        vn[c] = fact0 * (v[c * p.N + n] * fact1 + hdt * (a_old + f[c]));
+        xv[c] = x[c * p.N + n];
+        pv[c] = p.has_prev ? prev[c * p.N + n] : 0.f;
+        v_old[c] = v[c * p.N + n];
+        a_old[c] = a[c * p.N + n];
+      }
+      node_update<C>(p, w, xv, pv, v_old, a_old, true, f, vn, part);
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
         a[c * p.N + n] = f[c];
-        a2 = a2 + f[c] * f[c];
-        v2 = v2 + vn[c] * vn[c];
-        if (p.fire) {
-          part[0] = part[0] + f[c] * vn[c];
-          part[1 + c] = part[1 + c] + xv;
-        }
+        v[c * p.N + n] = vn[c];
       }
-      if (p.fire) {
-        const float a_norm = sqrtf(a2) + 1e-6f;
-        const float v_norm = sqrtf(v2);
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          vn[c] = vn[c] + alpha * (f[c] / a_norm * v_norm - vn[c]);
-          part[4 + c] = part[4 + c] + vn[c];
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < C; ++c) v[c * p.N + n] = vn[c];
     }
     if (p.fire)
       block_sum(part, 7, lds);  // ends with a barrier: positions may move again
@@ -1424,19 +1471,16 @@ integrate_shared2d_kernel(const float* x_in, const float* v_in, const float* a_i
       band_scalars(s, bd.sums, bd.n_bands, p, &o);
       s = o;
     } else if (!pending) {
-      s.gate = 1.f;
-      for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+      s = no_pending_update(s, s.dt);
     }
     // band mode: the scalars this step runs on are next step's starting point
     if (bd.sums && block == 0 && threadIdx.x == 0 && bd.ty_mode != 2) *scal_out = s;
   } else {
-    s.dt = p.vv_dt;
+    s = no_pending_update(Scalars(), p.vv_dt);
     s.alpha = 0.f;
     s.cap = fixed_cap;
-    s.gate = 1.f;
-    for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
   }
-  const float dt = s.dt, alpha = s.alpha, cap = s.cap;
+  const float dt = s.dt;
   const float c2 = 0.5f * (dt * dt);
   const bool fix = p.fire && pending;
 
@@ -1555,10 +1599,7 @@ integrate_shared2d_kernel(const float* x_in, const float* v_in, const float* a_i
                      ns[3][k + 1]);
   }
 
-  const float hdtg = (0.5f * dt) * p.gamma;
-  const float fact0 = 1.0f / (1.0f + hdtg);
-  const float fact1 = 1.0f - hdtg;
-  const float hdt = 0.5f * dt;
+  const StepLaw w = step_law(s.dt, s.alpha, s.cap, p.gamma);   // (s holds the fixed values without FIRE)
   float part[kNP];
   for (int i = 0; i < kNP; ++i) part[i] = 0.f;
 #pragma unroll
@@ -1590,14 +1631,16 @@ integrate_shared2d_kernel(const float* x_in, const float* v_in, const float* a_i
 #pragma unroll
       for (int c = 0; c < C; ++c) f[c] = f[c] - (okn[L] ? ns[L][k + 1][c] : 0.f);
     const long long n = base + (long long)gy * p.X + gx;
+    // (not node_update: its stores after the loop cost the band instance two more
+    // spilled VGPRs, scratch 28 -> 36 bytes)
     float a2 = 0.f, v2 = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const float xv = x_own[k][c];
-      if (p.has_prev) f[c] = f[c] + prev_pull(xv, pv_own[k][c], p.neg_k0, cap);
+      if (p.has_prev) f[c] = f[c] + prev_pull(xv, pv_own[k][c], p.neg_k0, w.cap);
       const float a_old = a_own[k][c];
       const float v_old = v_own[k][c];
-      vn[c] = fact0 * (v_old * fact1 + hdt * (a_old + f[c]));
+      vn[c] = w.fact0 * (v_old * w.fact1 + w.hdt * (a_old + f[c]));
       a_out[c * p.N + n] = f[c];
       if (FUSED) x_out[c * p.N + n] = xv;
       a2 = a2 + f[c] * f[c];
@@ -1608,13 +1651,9 @@ integrate_shared2d_kernel(const float* x_in, const float* v_in, const float* a_i
       }
     }
     if (p.fire) {
-      const float a_norm = sqrtf(a2) + 1e-6f;
-      const float v_norm = sqrtf(v2);
+      fire_mix<C>(f, vn, a2, v2, w.alpha);
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        vn[c] = vn[c] + alpha * (f[c] / a_norm * v_norm - vn[c]);
-        part[4 + c] = part[4 + c] + vn[c];
-      }
+      for (int c = 0; c < C; ++c) part[4 + c] = part[4 + c] + vn[c];
     }
 #pragma unroll
     for (int c = 0; c < C; ++c) v_out[c * p.N + n] = vn[c];
@@ -1777,9 +1816,7 @@ finish_kernel(float* __restrict__ x, float* __restrict__ v, MeshParams p,
     } else if (pending == 2) {
       s = *scal_in;
     } else {
-      s = *scal_in;
-      s.gate = 1.f;
-      for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
+      s = no_pending_update(*scal_in, scal_in->dt);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *scal_out = s;
   }
@@ -2053,6 +2090,94 @@ __device__ __forceinline__ void halo_coord(int h, int* hy, int* hx) {
   else { *hx = T + 1; *hy = h - 2 * (T + 2) - T + 1; }
 }
 
+// The frame both persistent kernels stand in: the workgroup's tile, the node a
+// thread owns and the halo slot it fills.  Threads beyond the T * T owners (the
+// speculative kernel's halo waves) own no node: inactive, at tile position (0, 0).
+template <int T>
+struct TileFrame {
+  int tx_i, ty_i, slice;   // this workgroup's tile
+  int ly, lx;              // the thread's node in the tile
+  int yi, xi;              // ... and in the plane
+  bool owner;              // the thread owns a node of the tile (tid < T * T)
+  bool active;             // an owner whose node lies inside the mesh
+  long long n;             // its index in a component array
+  int pidx;                // its perimeter index or -1
+  int hy, hx;              // halo slot of threads < kHalo, in xt coordinates
+  long long h_n;           // the slot's source node or -1 (none, or outside the mesh)
+
+  __device__ __forceinline__ TileFrame(const MeshParams& p, const PersistArgs& q) {
+    const int tid = threadIdx.x, wg = blockIdx.x;
+    owner = tid < Tile<T>::kThreads;
+    ly = owner ? tid / T : 0;
+    lx = owner ? tid % T : 0;
+    tx_i = wg % q.ntx;
+    ty_i = (wg / q.ntx) % q.nty;
+    slice = wg / (q.ntx * q.nty);
+    yi = ty_i * T + ly;
+    xi = tx_i * T + lx;
+    active = owner && yi < p.Y && xi < p.X;
+    const long long plane = (long long)p.Y * p.X;
+    n = slice * plane + (long long)yi * p.X + xi;
+    pidx = owner ? perim_index<T>(ly, lx) : -1;
+    hy = hx = 0;
+    h_n = -1;
+    if (tid < Tile<T>::kHalo) {
+      halo_coord<T>(tid, &hy, &hx);
+      const int gy = ty_i * T + hy - 1, gx = tx_i * T + hx - 1;
+      if (gy >= 0 && gy < p.Y && gx >= 0 && gx < p.X)
+        h_n = slice * plane + (long long)gy * p.X + gx;
+    }
+  }
+};
+
+// End of a chunk, called by every thread: the state goes to a staging set (xo, vo,
+// ao) -- persist_commit_kernel copies it over the caller's state only when NO
+// workgroup raised the abort flag, so a timeout leaves the caller's x, v, a
+// untouched as a whole -- and the workgroup's e_kin / v_max^2 and the scalars
+// follow.  `red`: LDS scratch of 2 * kWavesT floats.
+template <int T>
+__device__ __forceinline__ void persist_write_back(const TileFrame<T>& fr, const MeshParams& p,
+                                                   const PersistArgs& q, const Scalars& s,
+                                                   float x0, float x1, float v0, float v1,
+                                                   float a0, float a1, float* __restrict__ xo,
+                                                   float* __restrict__ vo,
+                                                   float* __restrict__ ao, float* red) {
+  const int tid = threadIdx.x, wg = blockIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  float ek = 0.f, vm2 = 0.f;
+  if (fr.active) {
+    xo[fr.n] = x0;
+    xo[p.N + fr.n] = x1;
+    vo[fr.n] = v0;
+    vo[p.N + fr.n] = v1;
+    ao[fr.n] = a0;
+    ao[p.N + fr.n] = a1;
+    ek = v0 * v0 + v1 * v1;
+    vm2 = ek;
+  }
+#pragma unroll
+  for (int dd = 32; dd > 0; dd >>= 1) {
+    ek = ek + __shfl_xor(ek, dd, 64);
+    vm2 = fmaxf(vm2, __shfl_xor(vm2, dd, 64));
+  }
+  __syncthreads();
+  if (lane == 0 && wave < Tile<T>::kWavesT) {
+    red[wave * 2] = ek;
+    red[wave * 2 + 1] = vm2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float e = 0.f, m = 0.f;
+    for (int w2 = 0; w2 < Tile<T>::kWavesT; ++w2) {
+      e = e + red[w2 * 2];
+      m = fmaxf(m, red[w2 * 2 + 1]);
+    }
+    q.stat_partials[wg * 2] = e;
+    q.stat_partials[wg * 2 + 1] = m;
+    if (wg == 0) *q.scal_out = s;
+  }
+}
+
 template <int T>
 __global__ void __launch_bounds__(T * T)
 mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
@@ -2069,27 +2194,10 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const int ly = tid / T, lx = tid % T;
   const int wg = blockIdx.x;
-  const int tx_i = wg % q.ntx;
-  const int ty_i = (wg / q.ntx) % q.nty;
-  const int slice = wg / (q.ntx * q.nty);
-  const int yi = ty_i * T + ly, xi = tx_i * T + lx;
-  const bool active = yi < p.Y && xi < p.X;
-  const long long plane = (long long)p.Y * p.X;
-  const long long n = slice * plane + (long long)yi * p.X + xi;
-  const int pidx = perim_index<T>(ly, lx);
+  const TileFrame<T> fr(p, q);
   const int nred = p.remove_drift ? 7 : 1;  // values exchanged per workgroup
 
-  // Halo slot owned by this thread (threads < kHalo): position + source node.
-  int hy = 0, hx = 0;
-  long long h_n = -1;
-  if (tid < TL::kHalo) {
-    halo_coord<T>(tid, &hy, &hx);
-    const int gy = ty_i * T + hy - 1, gx = tx_i * T + hx - 1;
-    if (gy >= 0 && gy < p.Y && gx >= 0 && gx < p.X)
-      h_n = slice * plane + (long long)gy * p.X + gx;
-  }
   // Granules this thread fetches in a collect: halo (slot relative offsets).
   long long h_off[TL::kHaloPolls];
   float* h_dst[TL::kHaloPolls];
@@ -2102,10 +2210,10 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
       const int h = t / kNodeGran, j = t - h * kNodeGran;
       int qy, qx;
       halo_coord<T>(h, &qy, &qx);
-      const int gy = ty_i * T + qy - 1, gx = tx_i * T + qx - 1;
+      const int gy = fr.ty_i * T + qy - 1, gx = fr.tx_i * T + qx - 1;
       if (gy >= 0 && gy < p.Y && gx >= 0 && gx < p.X) {
         const int oty = gy / T, otx = gx / T;
-        const int owg = (slice * q.nty + oty) * q.ntx + otx;
+        const int owg = (fr.slice * q.nty + oty) * q.ntx + otx;
         h_off[u] = (long long)owg * 2 * TL::kSlot +
                    perim_index<T>(gy - oty * T, gx - otx * T) * kNodeGran + j;
         h_dst[u] = &hval[h][j];
@@ -2115,70 +2223,38 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
 
   float x0 = 0.f, x1 = 0.f, v0 = 0.f, v1 = 0.f, a0 = 0.f, a1 = 0.f;
   float pr0 = 0.f, pr1 = 0.f;
-  if (active) {
-    x0 = xg[n];
-    x1 = xg[p.N + n];
-    v0 = vg[n];
-    v1 = vg[p.N + n];
+  if (fr.active) {
+    x0 = xg[fr.n];
+    x1 = xg[p.N + fr.n];
+    v0 = vg[fr.n];
+    v1 = vg[p.N + fr.n];
     if (p.has_prev) {
-      pr0 = prevg[n];
-      pr1 = prevg[p.N + n];
+      pr0 = prevg[fr.n];
+      pr1 = prevg[p.N + fr.n];
     }
   }
-  Scalars s = *q.scal_in;
-  s.gate = 1.f;
-  for (int c = 0; c < 3; ++c) s.mx[c] = s.mv[c] = 0.f;
-  if (!p.fire) s.dt = p.vv_dt;
+  Scalars s = no_pending_update(*q.scal_in, p.fire ? q.scal_in->dt : p.vv_dt);
   const float fixed_cap = q.cap0;
   float l0[4];
 #pragma unroll
   for (int L = 0; L < 4; ++L) l0[L] = vec_len(p.rest[L], 2);
 
+  // (pitch T + 3: xt[c] seen as one flat tile, this node at its centre)
   auto tile_force = [&](float* out) {
-    // identical operation order to node_force<2> with order2d; the four link
-    // families of build_params unrolled with compile-time directions
-    const float s0 = xt[0][ly + 1][lx + 1], s1 = xt[1][ly + 1][lx + 1];
-    float acc0 = 0.f, acc1 = 0.f;
-    // (branch free, see node_force_tile2d)
-#define SFM_FAR(L, DX, DY)                                                          \
-    {                                                                               \
-      const bool ok = xi - (DX) >= 0 && xi - (DX) < p.X && yi - (DY) >= 0 &&        \
-                      yi - (DY) < p.Y;                                              \
-      float f[2];                                                                   \
-      spring_xy<DX, DY>(s0 - xt[0][ly + 1 - (DY)][lx + 1 - (DX)] + p.rest[L][0],     \
-                        s1 - xt[1][ly + 1 - (DY)][lx + 1 - (DX)] + p.rest[L][1],     \
-                        l0[L], p.neg_k[L], p.prefer, f);                            \
-      acc0 = acc0 + (ok ? f[0] : 0.f);                                              \
-      acc1 = acc1 + (ok ? f[1] : 0.f);                                              \
-    }
-#define SFM_NEAR(L, DX, DY)                                                         \
-    {                                                                               \
-      const bool ok = xi + (DX) >= 0 && xi + (DX) < p.X && yi + (DY) >= 0 &&        \
-                      yi + (DY) < p.Y;                                              \
-      float f[2];                                                                   \
-      spring_xy<DX, DY>(xt[0][ly + 1 + (DY)][lx + 1 + (DX)] - s0 + p.rest[L][0],     \
-                        xt[1][ly + 1 + (DY)][lx + 1 + (DX)] - s1 + p.rest[L][1],     \
-                        l0[L], p.neg_k[L], p.prefer, f);                            \
-      acc0 = acc0 - (ok ? f[0] : 0.f);                                              \
-      acc1 = acc1 - (ok ? f[1] : 0.f);                                              \
-    }
-    SFM_FAR(0, 1, 0) SFM_FAR(1, 0, 1) SFM_FAR(2, 1, 1) SFM_FAR(3, -1, 1)
-    SFM_NEAR(0, 1, 0) SFM_NEAR(1, 0, 1) SFM_NEAR(2, 1, 1) SFM_NEAR(3, -1, 1)
-#undef SFM_FAR
-#undef SFM_NEAR
-    out[0] = acc0;
-    out[1] = acc1;
+    const int ctr = (fr.ly + 1) * (T + 3) + fr.lx + 1;
+    node_force_tile2d<T + 3>(&xt[0][0][0], &xt[1][0][0], ctr, p, fr.xi, fr.yi, xt[0][fr.ly + 1][fr.lx + 1],
+                             xt[1][fr.ly + 1][fr.lx + 1], l0, out);
   };
 
   // ---- a = F(x) + pull at the initial positions ------------------------------
-  xt[0][ly + 1][lx + 1] = x0;
-  xt[1][ly + 1][lx + 1] = x1;
-  if (h_n >= 0) {
-    xt[0][hy][hx] = xg[h_n];
-    xt[1][hy][hx] = xg[p.N + h_n];
+  xt[0][fr.ly + 1][fr.lx + 1] = x0;
+  xt[1][fr.ly + 1][fr.lx + 1] = x1;
+  if (fr.h_n >= 0) {
+    xt[0][fr.hy][fr.hx] = xg[fr.h_n];
+    xt[1][fr.hy][fr.hx] = xg[p.N + fr.h_n];
   }
   __syncthreads();
-  if (active) {
+  if (fr.active) {
     float f[2];
     tile_force(f);
     if (p.has_prev) {
@@ -2204,8 +2280,8 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
     const long long slot_off = (long long)(k & 1) * TL::kSlot;
     u64* my_slot = q.comm + (long long)wg * 2 * TL::kSlot + slot_off;
     // ---- publish the state after k - 1 steps ----------------------------------
-    if (!last && active && pidx >= 0) {
-      u64* g = my_slot + pidx * kNodeGran;
+    if (!last && fr.active && fr.pidx >= 0) {
+      u64* g = my_slot + fr.pidx * kNodeGran;
       put_granule(g + 0, epoch, x0);
       put_granule(g + 1, epoch, x1);
       put_granule(g + 2, epoch, v0);
@@ -2254,26 +2330,8 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
         if (lane == 63) sums[i] = t;
       }
       __syncthreads();
-      const float power = sums[0];
-      Scalars t = s;
-      const bool downhill = power >= 0.f;
-      t.n_pos = downhill ? s.n_pos + 1 : 0;
-      if (downhill) {
-        if (t.n_pos > p.n_min) {
-          t.dt = fminf(s.dt * p.f_inc, p.dt_cap);
-          t.alpha = s.alpha * p.f_alpha;
-        }
-        if (t.n_pos > 0 && (t.n_pos % p.cap_every) == 0) t.cap = p.cap_scale * s.cap;
-      } else {
-        t.dt = s.dt * p.f_dec;
-        t.alpha = p.alpha0;
-      }
-      t.cap = fminf(t.cap, p.final_cap);
-      t.gate = downhill ? 1.f : 0.f;
-      for (int c = 0; c < 3; ++c) {
-        t.mx[c] = p.remove_drift ? sums[1 + c] / p.n_f : 0.f;
-        t.mv[c] = p.remove_drift ? (sums[4 + c] / p.n_f) * t.gate : 0.f;
-      }
+      Scalars t;
+      scalars_from_sums(s, sums, p, &t);
       s = t;
       // pending gate / drift of step k - 1 on the node's own state
       v0 = v0 * s.gate;
@@ -2293,9 +2351,9 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
     const float c2 = 0.5f * (dt * dt);
     x0 = x0 + (dt * v0 + c2 * a0);
     x1 = x1 + (dt * v1 + c2 * a1);
-    xt[0][ly + 1][lx + 1] = x0;
-    xt[1][ly + 1][lx + 1] = x1;
-    if (h_n >= 0) {
+    xt[0][fr.ly + 1][fr.lx + 1] = x0;
+    xt[1][fr.ly + 1][fr.lx + 1] = x1;
+    if (fr.h_n >= 0) {
       float hx0 = hval[tid][0], hx1 = hval[tid][1];
       float hv0 = hval[tid][2], hv1 = hval[tid][3];
       if (reduce_now) {
@@ -2308,50 +2366,43 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
           hv1 = hv1 - s.mv[1];
         }
       }
-      xt[0][hy][hx] = hx0 + (dt * hv0 + c2 * hval[tid][4]);
-      xt[1][hy][hx] = hx1 + (dt * hv1 + c2 * hval[tid][5]);
+      xt[0][fr.hy][fr.hx] = hx0 + (dt * hv0 + c2 * hval[tid][4]);
+      xt[1][fr.hy][fr.hx] = hx1 + (dt * hv1 + c2 * hval[tid][5]);
     }
     __syncthreads();
     MTICK(2)
 
     // ---- integrate ------------------------------------------------------------------
     float part[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (active) {
-      const float cap = p.fire ? s.cap : fixed_cap;
-      const float hdtg = (0.5f * dt) * p.gamma;
-      const float fact0 = 1.0f / (1.0f + hdtg);
-      const float fact1 = 1.0f - hdtg;
-      const float hdt = 0.5f * dt;
+    if (fr.active) {
+      const StepLaw w = step_law(p, s, fixed_cap);
       float f[2];
       tile_force(f);
       if (p.has_prev) {
-        f[0] = f[0] + prev_pull(x0, pr0, p.neg_k0, cap);
-        f[1] = f[1] + prev_pull(x1, pr1, p.neg_k0, cap);
+        f[0] = f[0] + prev_pull(x0, pr0, p.neg_k0, w.cap);
+        f[1] = f[1] + prev_pull(x1, pr1, p.neg_k0, w.cap);
       }
-      float n0 = fact0 * (v0 * fact1 + hdt * (a0 + f[0]));
-      float n1 = fact0 * (v1 * fact1 + hdt * (a1 + f[1]));
+      float vn[2] = {w.fact0 * (v0 * w.fact1 + w.hdt * (a0 + f[0])),
+                     w.fact0 * (v1 * w.fact1 + w.hdt * (a1 + f[1]))};
       a0 = f[0];
       a1 = f[1];
       if (p.fire) {
         float a2 = 0.f, v2 = 0.f, pw = 0.f;
         a2 = a2 + f[0] * f[0];
-        v2 = v2 + n0 * n0;
-        pw = pw + f[0] * n0;
+        v2 = v2 + vn[0] * vn[0];
+        pw = pw + f[0] * vn[0];
         a2 = a2 + f[1] * f[1];
-        v2 = v2 + n1 * n1;
-        pw = pw + f[1] * n1;
+        v2 = v2 + vn[1] * vn[1];
+        pw = pw + f[1] * vn[1];
         part[0] = pw;
-        part[1] = x0;
+        part[1] = x0;   // (assigned, not added to zero: -0 stays -0)
         part[2] = x1;
-        const float a_norm = sqrtf(a2) + 1e-6f;
-        const float v_norm = sqrtf(v2);
-        n0 = n0 + s.alpha * (f[0] / a_norm * v_norm - n0);
-        n1 = n1 + s.alpha * (f[1] / a_norm * v_norm - n1);
-        part[4] = n0;
-        part[5] = n1;
+        fire_mix<2>(f, vn, a2, v2, w.alpha);
+        part[4] = vn[0];
+        part[5] = vn[1];
       }
-      v0 = n0;
-      v1 = n1;
+      v0 = vn[0];
+      v1 = vn[1];
     }
     MTICK(3)
     if (p.fire) {
@@ -2379,42 +2430,7 @@ mesh_persist2d_kernel(MeshParams p, const float* __restrict__ xg,
 #endif
 
   if (!ok) return;  // timed out (the abort flag is set)
-  // ---- write back, chunk statistics ------------------------------------------------
-  // The result goes to a staging set (xo, vo, ao); persist_commit_kernel copies
-  // it over the caller's state only when NO workgroup raised the abort flag, so
-  // a timeout leaves the caller's x, v, a untouched as a whole.
-  float ek = 0.f, vm2 = 0.f;
-  if (active) {
-    xo[n] = x0;
-    xo[p.N + n] = x1;
-    vo[n] = v0;
-    vo[p.N + n] = v1;
-    ao[n] = a0;
-    ao[p.N + n] = a1;
-    ek = v0 * v0 + v1 * v1;
-    vm2 = ek;
-  }
-#pragma unroll
-  for (int dd = 32; dd > 0; dd >>= 1) {
-    ek = ek + __shfl_xor(ek, dd, 64);
-    vm2 = fmaxf(vm2, __shfl_xor(vm2, dd, 64));
-  }
-  __syncthreads();
-  if (lane == 0) {
-    wred[wave][0] = ek;
-    wred[wave][1] = vm2;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float e = 0.f, m = 0.f;
-    for (int w2 = 0; w2 < TL::kWavesT; ++w2) {
-      e = e + wred[w2][0];
-      m = fmaxf(m, wred[w2][1]);
-    }
-    q.stat_partials[wg * 2] = e;
-    q.stat_partials[wg * 2 + 1] = m;
-    if (wg == 0) *q.scal_out = s;
-  }
+  persist_write_back(fr, p, q, s, x0, x1, v0, v1, a0, a1, xo, vo, ao, &wred[0][0]);
 }
 
 // ---------------------------------------------------------------------------
@@ -2496,26 +2512,9 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
     lds_barrier();
     return s_fail == 0;
   };
-  const bool owner = tid < NM;            // (the halo waves own no node)
-  const int ly = owner ? tid / T : 0, lx = owner ? tid % T : 0;
   const int wg = blockIdx.x;
-  const int tx_i = wg % q.ntx;
-  const int ty_i = (wg / q.ntx) % q.nty;
-  const int slice = wg / (q.ntx * q.nty);
-  const int yi = ty_i * T + ly, xi = tx_i * T + lx;
-  const bool active = owner && yi < p.Y && xi < p.X;
-  const long long plane = (long long)p.Y * p.X;
-  const long long n = slice * plane + (long long)yi * p.X + xi;
-  const int pidx = owner ? perim_index<T>(ly, lx) : -1;
+  const TileFrame<T> fr(p, q);
 
-  int hy = 0, hx = 0;
-  long long h_n = -1;
-  if (tid < TL::kHalo) {
-    halo_coord<T>(tid, &hy, &hx);
-    const int gy = ty_i * T + hy - 1, gx = tx_i * T + hx - 1;
-    if (gy >= 0 && gy < p.Y && gx >= 0 && gx < p.X)
-      h_n = slice * plane + (long long)gy * p.X + gx;
-  }
   // byte offset (slot parity 0) of the downhill pair of halo node tid + u NT in the
   // exchange area, or -1; the uphill pair follows it
   const __amdgpu_buffer_rsrc_t comm_rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -2530,10 +2529,10 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
     if (h < TL::kHalo) {
       int qy, qx;
       halo_coord<T>(h, &qy, &qx);
-      const int gy = ty_i * T + qy - 1, gx = tx_i * T + qx - 1;
+      const int gy = fr.ty_i * T + qy - 1, gx = fr.tx_i * T + qx - 1;
       if (gy >= 0 && gy < p.Y && gx >= 0 && gx < p.X) {
         const int oty = gy / T, otx = gx / T;
-        const int owg = (slice * q.nty + oty) * q.ntx + otx;
+        const int owg = (fr.slice * q.nty + oty) * q.ntx + otx;
         h_off[u] = (owg * 2 * kSlotS + perim_index<T>(gy - oty * T, gx - otx * T) * kGranS) *
                    static_cast<int>(sizeof(u64));
         h_dst[u] = &hval[h][0];
@@ -2543,14 +2542,14 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
 
   float x0 = 0.f, x1 = 0.f, v0 = 0.f, v1 = 0.f, a0 = 0.f, a1 = 0.f;
   float pr0 = 0.f, pr1 = 0.f;
-  if (active) {
-    x0 = xg[n];
-    x1 = xg[p.N + n];
-    v0 = vg[n];
-    v1 = vg[p.N + n];
+  if (fr.active) {
+    x0 = xg[fr.n];
+    x1 = xg[p.N + fr.n];
+    v0 = vg[fr.n];
+    v1 = vg[p.N + fr.n];
     if (p.has_prev) {
-      pr0 = prevg[n];
-      pr1 = prevg[p.N + n];
+      pr0 = prevg[fr.n];
+      pr1 = prevg[p.N + fr.n];
     }
   }
   Scalars s = *q.scal_in;
@@ -2566,7 +2565,7 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
   //   link 2 (1, 1):  (0, 0..T-1), (1..T-1, 0)               2 T - 1
   //   link 3 (-1, 1): (0, 2..T+1), (1..T-1, T+1)             2 T - 1
   int hs_y = 0, hs_x = 0, hs_L = -1, hs_dx = 0, hs_dy = 0;
-  if (SH && !owner) {
+  if (SH && !fr.owner) {
     const int i = tid - NM;
     if (i < T) { hs_L = 0; hs_y = 1 + i; hs_x = 0; }
     else if (i < 2 * T) { hs_L = 1; hs_y = 0; hs_x = 1 + (i - T); }
@@ -2640,17 +2639,17 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
   // Net spring force on this thread's node from the positions in xt.  Contains
   // a barrier when SH: called by ALL threads.
   auto tile_force = [&](float* out) {
-    const float s0 = xt[0][ly + 1][lx + 1], s1 = xt[1][ly + 1][lx + 1];
-    float acc0 = 0.f, acc1 = 0.f;
+    const float s0 = xt[0][fr.ly + 1][fr.lx + 1], s1 = xt[1][fr.ly + 1][fr.lx + 1];
     if constexpr (SH) {
+      float acc0 = 0.f, acc1 = 0.f;
       float nr[4][2];
-      if (owner) {
+      if (fr.owner) {
 #define SFM_NEAR_EVAL(L, DX, DY)                                                    \
-        spring_xy<DX, DY>(xt[0][ly + 1 + (DY)][lx + 1 + (DX)] - s0 + p.rest[L][0],   \
-                          xt[1][ly + 1 + (DY)][lx + 1 + (DX)] - s1 + p.rest[L][1],   \
+        spring_xy<DX, DY>(xt[0][fr.ly + 1 + (DY)][fr.lx + 1 + (DX)] - s0 + p.rest[L][0],   \
+                          xt[1][fr.ly + 1 + (DY)][fr.lx + 1 + (DX)] - s1 + p.rest[L][1],   \
                           l0[L], p.neg_k[L], p.prefer, nr[L]);                      \
-        nf[L][0][ly + 1][lx + 1] = nr[L][0];                                        \
-        nf[L][1][ly + 1][lx + 1] = nr[L][1];
+        nf[L][0][fr.ly + 1][fr.lx + 1] = nr[L][0];                                        \
+        nf[L][1][fr.ly + 1][fr.lx + 1] = nr[L][1];
         SFM_NEAR_EVAL(0, 1, 0) SFM_NEAR_EVAL(1, 0, 1) SFM_NEAR_EVAL(2, 1, 1)
         SFM_NEAR_EVAL(3, -1, 1)
 #undef SFM_NEAR_EVAL
@@ -2665,91 +2664,48 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
       lds_barrier();
 #define SFM_FAR_ADD(L, DX, DY)                                                      \
       {                                                                             \
-        const bool ok = xi - (DX) >= 0 && xi - (DX) < p.X && yi - (DY) >= 0 &&      \
-                        yi - (DY) < p.Y;                                            \
-        const float f0 = nf[L][0][ly + 1 - (DY)][lx + 1 - (DX)];                    \
-        const float f1 = nf[L][1][ly + 1 - (DY)][lx + 1 - (DX)];                    \
+        const bool ok = fr.xi - (DX) >= 0 && fr.xi - (DX) < p.X && fr.yi - (DY) >= 0 &&      \
+                        fr.yi - (DY) < p.Y;                                            \
+        const float f0 = nf[L][0][fr.ly + 1 - (DY)][fr.lx + 1 - (DX)];                    \
+        const float f1 = nf[L][1][fr.ly + 1 - (DY)][fr.lx + 1 - (DX)];                    \
         acc0 = acc0 + (ok ? f0 : 0.f);                                              \
         acc1 = acc1 + (ok ? f1 : 0.f);                                              \
       }
 #define SFM_NEAR_SUB(L, DX, DY)                                                     \
       {                                                                             \
-        const bool ok = xi + (DX) >= 0 && xi + (DX) < p.X && yi + (DY) >= 0 &&      \
-                        yi + (DY) < p.Y;                                            \
+        const bool ok = fr.xi + (DX) >= 0 && fr.xi + (DX) < p.X && fr.yi + (DY) >= 0 &&      \
+                        fr.yi + (DY) < p.Y;                                            \
         acc0 = acc0 - (ok ? nr[L][0] : 0.f);                                        \
         acc1 = acc1 - (ok ? nr[L][1] : 0.f);                                        \
       }
-      if (owner) {
+      if (fr.owner) {
         SFM_FAR_ADD(0, 1, 0) SFM_FAR_ADD(1, 0, 1) SFM_FAR_ADD(2, 1, 1) SFM_FAR_ADD(3, -1, 1)
         SFM_NEAR_SUB(0, 1, 0) SFM_NEAR_SUB(1, 0, 1) SFM_NEAR_SUB(2, 1, 1) SFM_NEAR_SUB(3, -1, 1)
       }
 #undef SFM_FAR_ADD
 #undef SFM_NEAR_SUB
+      out[0] = acc0;
+      out[1] = acc1;
     } else {
-#define SFM_FAR(L, DX, DY)                                                          \
-    {                                                                               \
-      const bool ok = xi - (DX) >= 0 && xi - (DX) < p.X && yi - (DY) >= 0 &&        \
-                      yi - (DY) < p.Y;                                              \
-      float f[2];                                                                   \
-      spring_xy<DX, DY>(s0 - xt[0][ly + 1 - (DY)][lx + 1 - (DX)] + p.rest[L][0],     \
-                        s1 - xt[1][ly + 1 - (DY)][lx + 1 - (DX)] + p.rest[L][1],     \
-                        l0[L], p.neg_k[L], p.prefer, f);                            \
-      acc0 = acc0 + (ok ? f[0] : 0.f);                                              \
-      acc1 = acc1 + (ok ? f[1] : 0.f);                                              \
+      node_force_tile2d<T + 3>(&xt[0][0][0], &xt[1][0][0], (fr.ly + 1) * (T + 3) + fr.lx + 1, p, fr.xi, fr.yi,
+                               s0, s1, l0, out);
     }
-#define SFM_NEAR(L, DX, DY)                                                         \
-    {                                                                               \
-      const bool ok = xi + (DX) >= 0 && xi + (DX) < p.X && yi + (DY) >= 0 &&        \
-                      yi + (DY) < p.Y;                                              \
-      float f[2];                                                                   \
-      spring_xy<DX, DY>(xt[0][ly + 1 + (DY)][lx + 1 + (DX)] - s0 + p.rest[L][0],     \
-                        xt[1][ly + 1 + (DY)][lx + 1 + (DX)] - s1 + p.rest[L][1],     \
-                        l0[L], p.neg_k[L], p.prefer, f);                            \
-      acc0 = acc0 - (ok ? f[0] : 0.f);                                              \
-      acc1 = acc1 - (ok ? f[1] : 0.f);                                              \
-    }
-    SFM_FAR(0, 1, 0) SFM_FAR(1, 0, 1) SFM_FAR(2, 1, 1) SFM_FAR(3, -1, 1)
-    SFM_NEAR(0, 1, 0) SFM_NEAR(1, 0, 1) SFM_NEAR(2, 1, 1) SFM_NEAR(3, -1, 1)
-#undef SFM_FAR
-#undef SFM_NEAR
-    }
-    out[0] = acc0;
-    out[1] = acc1;
-  };
-
-  // FIRE scalar update of mesh.py:459-490 for a known sign of the power.
-  auto next_scalars = [&](const Scalars& in, bool downhill) -> Scalars {
-    Scalars t = in;
-    t.n_pos = downhill ? in.n_pos + 1 : 0;
-    if (downhill) {
-      if (t.n_pos > p.n_min) {
-        t.dt = fminf(in.dt * p.f_inc, p.dt_cap);
-        t.alpha = in.alpha * p.f_alpha;
-      }
-      if (t.n_pos > 0 && (t.n_pos % p.cap_every) == 0) t.cap = p.cap_scale * in.cap;
-    } else {
-      t.dt = in.dt * p.f_dec;
-      t.alpha = p.alpha0;
-    }
-    t.cap = fminf(t.cap, p.final_cap);
-    t.gate = downhill ? 1.f : 0.f;
-    return t;
   };
 
   // a = F(x) + pull at the initial positions
-  if (owner) {
-    xt[0][ly + 1][lx + 1] = x0;
-    xt[1][ly + 1][lx + 1] = x1;
+  if (fr.owner) {
+    xt[0][fr.ly + 1][fr.lx + 1] = x0;
+    xt[1][fr.ly + 1][fr.lx + 1] = x1;
   }
-  if (h_n >= 0) {
-    xt[0][hy][hx] = xg[h_n];
-    xt[1][hy][hx] = xg[p.N + h_n];
+  if (fr.h_n >= 0) {
+    xt[0][fr.hy][fr.hx] = xg[fr.h_n];
+    xt[1][fr.hy][fr.hx] = xg[p.N + fr.h_n];
   }
   __syncthreads();
   {
     float f[2] = {0.f, 0.f};
-    if (SH || active) tile_force(f);
-    if (active) {
+    if (SH || fr.active) tile_force(f);
+    if (fr.active) {
     if (p.has_prev) {
       f[0] = f[0] + prev_pull(x0, pr0, p.neg_k0, s.cap);
       f[1] = f[1] + prev_pull(x1, pr1, p.neg_k0, s.cap);
@@ -2769,16 +2725,16 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
   // bit 24 set when the step was redone on the uphill branch: readers know
   // which of the two they need, because everyone takes the same decisions.
   // `sk`: the scalars the published state was stepped with; the next step runs on
-  // next_scalars(sk, true) with the gate open, or, redone, on next_scalars(sk, false)
+  // fire_next(sk, true, p) with the gate open, or, redone, on fire_next(sk, false, p)
   // with v gated to zero (`first`: the initial state, stepped with `sk` itself).
   // The two expressions are do_step's position update of an own node.
   auto publish = [&](int step, unsigned tag, const Scalars& sk, bool first) {
     u64* slot = q.comm + (long long)wg * 2 * kSlotS + (long long)((step + 1) & 1) * kSlotS;
-    if (active && pidx >= 0) {
-      const Scalars sd = first ? sk : next_scalars(sk, true);
+    if (fr.active && fr.pidx >= 0) {
+      const Scalars sd = first ? sk : fire_next(sk, true, p);
       const float dtd = sd.dt, c2d = 0.5f * (dtd * dtd);
       const float vd0 = v0 * 1.f, vd1 = v1 * 1.f;
-      u64* g = slot + pidx * kGranS;
+      u64* g = slot + fr.pidx * kGranS;
       put_granule(g + 0, tag, x0 + (dtd * vd0 + c2d * a0));
       put_granule(g + 1, tag, x1 + (dtd * vd1 + c2d * a1));
     }
@@ -2788,11 +2744,11 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
   auto publish_uphill = [&](int step, unsigned tag, const Scalars& sk, float xs0, float xs1,
                             float vs0, float vs1, float as0, float as1) {
     u64* slot = q.comm + (long long)wg * 2 * kSlotS + (long long)((step + 1) & 1) * kSlotS;
-    if (active && pidx >= 0) {
-      const Scalars su = next_scalars(sk, false);
+    if (fr.active && fr.pidx >= 0) {
+      const Scalars su = fire_next(sk, false, p);
       const float dtu = su.dt, c2u = 0.5f * (dtu * dtu);
       const float vu0 = vs0 * 0.f, vu1 = vs1 * 0.f;
-      u64* g = slot + pidx * kGranS;
+      u64* g = slot + fr.pidx * kGranS;
       put_granule(g + 2, tag, xs0 + (dtu * vu0 + c2u * as0));
       put_granule(g + 3, tag, xs1 + (dtu * vu1 + c2u * as1));
     }
@@ -2820,48 +2776,42 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
     const float c2 = 0.5f * (dt * dt);
     x0 = x0 + (dt * v0 + c2 * a0);
     x1 = x1 + (dt * v1 + c2 * a1);
-    if (owner) {
-      xt[0][ly + 1][lx + 1] = x0;
-      xt[1][ly + 1][lx + 1] = x1;
+    if (fr.owner) {
+      xt[0][fr.ly + 1][fr.lx + 1] = x0;
+      xt[1][fr.ly + 1][fr.lx + 1] = x1;
     }
-    if (h_n >= 0) {   // (the owner evaluated this update: see publish)
+    if (fr.h_n >= 0) {   // (the owner evaluated this update: see publish)
       const int cand = gate == 0.f ? 2 : 0;
-      xt[0][hy][hx] = hval[tid][cand];
-      xt[1][hy][hx] = hval[tid][cand + 1];
+      xt[0][fr.hy][fr.hx] = hval[tid][cand];
+      xt[1][fr.hy][fr.hx] = hval[tid][cand + 1];
     }
     lds_barrier();
     issue_early();
     STICK(5)
     float pw = 0.f;
     float f[2] = {0.f, 0.f};
-    if (SH || active) tile_force(f);
+    if (SH || fr.active) tile_force(f);
     STICK(6)
-    if (active) {
-      const float hdtg = (0.5f * dt) * p.gamma;
-      const float fact0 = 1.0f / (1.0f + hdtg);
-      const float fact1 = 1.0f - hdtg;
-      const float hdt = 0.5f * dt;
+    if (fr.active) {
+      const StepLaw w = step_law(sk.dt, sk.alpha, sk.cap, p.gamma);   // (FIRE only)
       if (p.has_prev) {
-        f[0] = f[0] + prev_pull(x0, pr0, p.neg_k0, sk.cap);
-        f[1] = f[1] + prev_pull(x1, pr1, p.neg_k0, sk.cap);
+        f[0] = f[0] + prev_pull(x0, pr0, p.neg_k0, w.cap);
+        f[1] = f[1] + prev_pull(x1, pr1, p.neg_k0, w.cap);
       }
-      float n0 = fact0 * (v0 * fact1 + hdt * (a0 + f[0]));
-      float n1 = fact0 * (v1 * fact1 + hdt * (a1 + f[1]));
+      float vn[2] = {w.fact0 * (v0 * w.fact1 + w.hdt * (a0 + f[0])),
+                     w.fact0 * (v1 * w.fact1 + w.hdt * (a1 + f[1]))};
       a0 = f[0];
       a1 = f[1];
       float a2 = 0.f, v2 = 0.f;
       a2 = a2 + f[0] * f[0];
-      v2 = v2 + n0 * n0;
-      pw = pw + f[0] * n0;
+      v2 = v2 + vn[0] * vn[0];
+      pw = pw + f[0] * vn[0];
       a2 = a2 + f[1] * f[1];
-      v2 = v2 + n1 * n1;
-      pw = pw + f[1] * n1;
-      const float a_norm = sqrtf(a2) + 1e-6f;
-      const float v_norm = sqrtf(v2);
-      n0 = n0 + sk.alpha * (f[0] / a_norm * v_norm - n0);
-      n1 = n1 + sk.alpha * (f[1] / a_norm * v_norm - n1);
-      v0 = n0;
-      v1 = n1;
+      v2 = v2 + vn[1] * vn[1];
+      pw = pw + f[1] * vn[1];
+      fire_mix<2>(f, vn, a2, v2, w.alpha);
+      v0 = vn[0];
+      v1 = vn[1];
     }
     STICK(7)
     publish(step, tag, sk, false);   // the state is final: out before the power reduction
@@ -2934,7 +2884,7 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
     early_tag = want_tag;
     Scalars s_try = s;
     if (!last) {
-      if (k > 1) s_try = next_scalars(s_before, true);
+      if (k > 1) s_try = fire_next(s_before, true, p);
       do_step(s_try, 1.f, k, static_cast<unsigned>(k + 1));
     }
     issue_early();   // (last iteration: there was no step)
@@ -2961,7 +2911,7 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
     STICK(3)
     const bool downhill = s_power >= 0.f;
     if (last) {
-      s = next_scalars(s_before, downhill);
+      s = fire_next(s_before, downhill, p);
       v0 = v0 * s.gate;
       v1 = v1 * s.gate;
       break;
@@ -2977,7 +2927,7 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
       v1 = bv1;
       a0 = ba0;
       a1 = ba1;
-      s = next_scalars(s_before, false);
+      s = fire_next(s_before, false, p);
       publish_uphill(k - 1, want_tag, s_before, x0, x1, v0, v1, a0, a1);
       {
         // the neighbours' uphill candidates of the state after k - 1 steps (same
@@ -3011,39 +2961,8 @@ mesh_persist2d_spec_kernel(MeshParams p, const float* __restrict__ xg,
            st[8] / q.num_iters, st[9] / q.num_iters);
 #endif
   if (!ok) return;  // timed out (the abort flag is set)
-  float ek = 0.f, vm2 = 0.f;
-  if (active) {
-    xo[n] = x0;
-    xo[p.N + n] = x1;
-    vo[n] = v0;
-    vo[p.N + n] = v1;
-    ao[n] = a0;
-    ao[p.N + n] = a1;
-    ek = v0 * v0 + v1 * v1;
-    vm2 = ek;
-  }
-#pragma unroll
-  for (int dd = 32; dd > 0; dd >>= 1) {
-    ek = ek + __shfl_xor(ek, dd, 64);
-    vm2 = fmaxf(vm2, __shfl_xor(vm2, dd, 64));
-  }
   __shared__ float fin[TL::kWavesT][2];
-  __syncthreads();
-  if (lane == 0 && wave < TL::kWavesT) {
-    fin[wave][0] = ek;
-    fin[wave][1] = vm2;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float e = 0.f, m = 0.f;
-    for (int w2 = 0; w2 < TL::kWavesT; ++w2) {
-      e = e + fin[w2][0];
-      m = fmaxf(m, fin[w2][1]);
-    }
-    q.stat_partials[wg * 2] = e;
-    q.stat_partials[wg * 2 + 1] = m;
-    if (wg == 0) *q.scal_out = s;
-  }
+  persist_write_back(fr, p, q, s, x0, x1, v0, v1, a0, a1, xo, vo, ao, &fin[0][0]);
 }
 
 // All-or-nothing hand-over of the persistent kernel's result.

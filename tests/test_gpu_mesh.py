@@ -408,6 +408,12 @@ def _with_env(env, fn):
         os.environ[k] = v
 
 
+def _device_cus():
+  """Compute units of the current device (what the chunk planner compares with)."""
+  import torch
+  return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('variant', ['fire', 'fire_drift', 'verlet', 'no_prev',
                                      'wide'])
@@ -442,6 +448,12 @@ def test_integrator_paths_agree(gpu, variant):
       'tiled': _with_env({'SFM_MESH_PERSISTENT': '0'}, run),
       'multi': _with_env({'SFM_MESH_PERSISTENT': '0', 'SFM_MESH_TILED': '0'}, run),
   }
+  if variant in ('fire_drift', 'verlet'):
+    # these cannot speculate: mesh_persist2d_kernel<32>, 2 x 3 tiles x 3 slices.
+    # plan_chunk takes the persistent path at the tile SFM_MESH_TILE names only when
+    # the workgroups fit the chip (nw <= kMaxWg && nw <= CUs): 18 here
+    assert 3 * -(-40 // 32) * -(-70 // 32) == 18 <= _device_cus()
+    res['default32'] = _with_env({'SFM_MESH_TILE': '32'}, run)
   wx, we, wt = mesh_oracle.relax_mesh(x0.copy(), None if pv is None else pv.copy(),
                                       cfg)
   scale = np.abs(wx).max()
@@ -449,7 +461,7 @@ def test_integrator_paths_agree(gpu, variant):
     assert gt == wt, name
     np.testing.assert_allclose(np.array(gx), wx, atol=1e-3 * scale, err_msg=name)
     np.testing.assert_allclose(ge, we, rtol=1e-3, err_msg=name)
-  for name in ('default', 'tiled'):
+  for name in set(res) - {'multi'}:
     np.testing.assert_allclose(np.array(res[name][0]), np.array(res['multi'][0]),
                                atol=2e-4 * scale, err_msg=name)
 
@@ -561,8 +573,15 @@ def test_three_pass_relaxation_driver_vs_reference_output(gpu, golden, case):
   np.testing.assert_allclose(ge, g[f'{case}_ekin'], rtol=1e-3, atol=1e-6)
 
 
+# (2, 2, 33, 70) runs under SFM_MESH_TILE=32 (what multi-slice meshes with more than
+# 256 tiles of 16 run): 2 x 3 tiles x 2 slices, ragged in both axes -- an interior
+# edge, a ragged edge and a slice boundary at once
+_SPEC_TILE32 = (2, 2, 33, 70)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('shape', [(2, 1, 205, 205), (2, 3, 40, 70), (2, 1, 33, 300)])
+@pytest.mark.parametrize('shape', [(2, 1, 205, 205), (2, 3, 40, 70), (2, 1, 33, 300),
+                                   _SPEC_TILE32])
 def test_speculative_fire_is_bit_identical(gpu, shape):
   """mesh_persist2d_spec_kernel runs every step on the downhill branch and
   redoes it when the power turns out negative: bit-identical to the kernel
@@ -577,16 +596,22 @@ def test_speculative_fire_is_bit_identical(gpu, shape):
                                num_iters=150, max_iters=450, stop_v_max=1e-9, dt_max=1000,
                                start_cap=0.01, final_cap=10, prefer_orig_order=True)
   x0 = np.zeros(shape, np.float32)
+  env = {}
+  if shape == _SPEC_TILE32:
+    # plan_chunk takes tile 32 only when its workgroups fit the chip
+    # (nw <= kMaxWg && nw <= CUs): 12 here
+    assert 2 * -(-33 // 32) * -(-70 // 32) == 12 <= _device_cus()
+    env = {'SFM_MESH_TILE': '32'}
   vv = lambda: mesh.velocity_verlet(x0, np.zeros_like(x0), prev, cfg, cfg.start_cap)
-  a = _with_env({'SFM_MESH_SPECULATE': '1'}, vv)
-  b = _with_env({'SFM_MESH_SPECULATE': '0'}, vv)
+  a = _with_env(dict(env, SFM_MESH_SPECULATE='1'), vv)
+  b = _with_env(dict(env, SFM_MESH_SPECULATE='0'), vv)
   for u, w in zip(a[:3], b[:3]):
     np.testing.assert_array_equal(np.array(u), np.array(w))
   assert a[3:] == b[3:]
   assert a[5] < 150          # the power went negative at least once in the chunk
   run = lambda: mesh.relax_mesh(x0, prev, cfg)
-  c = _with_env({'SFM_MESH_SPECULATE': '1'}, run)
-  d = _with_env({'SFM_MESH_SPECULATE': '0'}, run)
+  c = _with_env(dict(env, SFM_MESH_SPECULATE='1'), run)
+  d = _with_env(dict(env, SFM_MESH_SPECULATE='0'), run)
   np.testing.assert_array_equal(np.array(c[0]), np.array(d[0]))
   assert c[1] == d[1] and c[2] == d[2]
   wx, we, wt = mesh_oracle.relax_mesh(x0, prev, cfg)
