@@ -1061,108 +1061,128 @@ compact_surface_kernel(const float* __restrict__ src, float* __restrict__ dst,
 }
 
 struct PeakWs {
-  int* idx1;
-  float* v1;
-  int* zero_is_peak;
-  int* cand_count;
-  float* cand_val;
-  int* cand_idx;
-  unsigned int* bitmap;
-  int group, bitmap_words;
+  sfm::FusedPeaks f;   // what the fused matrix-core pass shares with the peak kernels
   unsigned int* smax;
   float* blkmax;       // masked MFMA path only: [batch, kBlkMaxN]
   unsigned long long* best;
-  int* hot_count;      // fused MFMA path only
-  int* skipmask;       // fused MFMA path: pruned row tiles per surface
-  float* hot_val;
-  int* hot_idx;
-  size_t zero_from, zero_bytes;  // region that must be cleared per batch
+  char* zero;          // state that clear_peak_state() clears per batch
+  size_t zero_bytes;
   size_t bytes;
 };
 
 constexpr int kBlkMaxN = 16;   // blocks of sfm::kMaskedBlkRows rows: surfaces up to 512 rows
 
+// hot: the hot lists of the fused MFMA path; blk: the block maxima of the masked one.
 PeakWs carve_peaks(sfm::Carver& c, int batch, long long sn, bool hot = false,
                    int group = 0, bool blk = false) {
   PeakWs w;
+  sfm::FusedPeaks& f = w.f;
   w.blkmax = blk ? c.take<float>((size_t)batch * kBlkMaxN) : nullptr;
-  w.group = group > 0 && group < batch ? group : batch;
-  w.bitmap_words = static_cast<int>((sn + 31) / 32);
-  w.idx1 = c.take<int>(batch);
-  w.v1 = c.take<float>(batch);
-  w.hot_val = hot ? c.take<float>((size_t)batch * kHotCap) : nullptr;
-  w.hot_idx = hot ? c.take<int>((size_t)batch * kHotCap) : nullptr;
-  w.cand_val = c.take<float>((size_t)batch * kCandCap);
-  w.cand_idx = c.take<int>((size_t)batch * kCandCap);
+  f.group = group > 0 && group < batch ? group : batch;
+  f.bitmap_words = static_cast<int>((sn + 31) / 32);
+  f.idx1 = c.take<int>(batch);
+  f.v1 = c.take<float>(batch);
+  f.hot_cap = kHotCap;
+  f.hot_val = hot ? c.take<float>((size_t)batch * kHotCap) : nullptr;
+  f.hot_idx = hot ? c.take<int>((size_t)batch * kHotCap) : nullptr;
+  f.cand_cap = kCandCap;
+  f.cand_val = c.take<float>((size_t)batch * kCandCap);
+  f.cand_idx = c.take<int>((size_t)batch * kCandCap);
   const size_t z0 = sfm::align_up(c.off, 256);
-  w.zero_is_peak = c.take<int>(batch);
-  w.cand_count = c.take<int>(batch);
-  w.hot_count = c.take<int>(batch);
-  w.skipmask = c.take<int>(batch);
+  f.zero_is_peak = c.take<int>(batch);
+  f.cand_count = c.take<int>(batch);
+  f.hot_count = c.take<int>(batch);
+  f.skipmask = c.take<int>(batch);
   w.smax = c.take<unsigned int>(batch);
   w.best = c.take<unsigned long long>(batch);
-  w.bitmap = c.take<unsigned int>(
-      (size_t)((batch + w.group - 1) / w.group) * w.bitmap_words);
-  w.zero_from = z0;
+  f.bitmap = c.take<unsigned int>((size_t)((batch + f.group - 1) / f.group) * f.bitmap_words);
+  w.zero = c.base ? c.base + z0 : nullptr;
   w.zero_bytes = c.total() - z0;
   w.bytes = c.total();
   return w;
 }
 
-int run_peaks(const PeakWs& w, char* ws_base, const float* surf, int pitch,
-              long long bstride, int nd, const int* S, long long sn, int batch,
-              const float* center,
-              int min_distance, float threshold_rel, const int* radius,
-              float* out, hipStream_t st, bool first_pass_done = false,
-              bool smax_done = false, const unsigned int* live_ovmax = nullptr,
-              const int* live_geo = nullptr, bool use_blkmax = false,
-              bool nans = false) {
-  PeakArgs p;
-  p.blkmax = use_blkmax ? w.blkmax : nullptr;
-  p.blk_rows = sfm::kMaskedBlkRows;
-  p.blk_n = (S[1] + sfm::kMaskedBlkRows - 1) / sfm::kMaskedBlkRows;
-  p.live_ovmax = live_ovmax;
-  p.live_py = live_geo ? live_geo[0] : 0;
-  p.live_qy = live_geo ? live_geo[1] : 0;
-  p.live_qx = live_geo ? live_geo[2] : 0;
-  p.surf = surf;
-  p.nd = nd;
+// The per-batch peak state is cleared once per batch, before the first kernel that
+// writes it.  That is the surface producer when it runs the first peak pass or
+// delivers the surface maxima (PeakDone): the driver clears before it launches one.
+// Otherwise run_peaks clears.
+int clear_peak_state(const PeakWs& w, hipStream_t st) {
+  SFM_HIP_CHECK(hipMemsetAsync(w.zero, 0, w.zero_bytes, st));
+  return SFM_OK;
+}
+
+int check_workspace(const char* unit, const void* ws, size_t have, size_t need) {
+  if (!ws || have < need)
+    return sfm::fail(SFM_ERR_WORKSPACE, "%s workspace needs %zu bytes, got %zu", unit,
+                     need, have);
+  return SFM_OK;
+}
+
+struct SurfaceLayout {
+  const float* surf;  // [batch, S] with the row pitch and per-surface stride below
+  int nd;
+  const int* S;       // [z]yx
+  long long Sn;
+  int pitch;
+  long long bstride;
+  int batch;
+};
+
+// Desc: SfmXcorrDesc or SfmPeaksDesc, for the peak parameters they share.
+template <typename Desc>
+PeakArgs make_peak_args(const PeakWs& w, const SurfaceLayout& s, const Desc& q,
+                        const float* center, float* out) {
+  PeakArgs p = {};  // the masked matrix-core extras (live_*, blkmax) stay off
+  p.surf = s.surf;
+  p.nd = s.nd;
   for (int i = 0; i < 3; ++i) {
-    p.S[i] = S[i];
+    p.S[i] = s.S[i];
     p.center[i] = center[i];
-    p.radius[i] = radius[i];
+    p.radius[i] = q.peak_radius[i];
   }
-  p.Sn = sn;
-  p.pitch = pitch;
-  p.bstride = bstride;
-  p.batch = batch;
-  p.min_distance = min_distance;
-  p.threshold_rel = threshold_rel;
-  p.idx1 = w.idx1;
-  p.v1 = w.v1;
-  p.zero_is_peak = w.zero_is_peak;
-  p.skipmask = w.skipmask;
-  p.cand_count = w.cand_count;
-  p.cand_val = w.cand_val;
-  p.cand_idx = w.cand_idx;
-  p.bitmap = w.bitmap;
-  p.group = w.group;
-  p.bitmap_words = w.bitmap_words;
+  p.Sn = s.Sn;
+  p.pitch = s.pitch;
+  p.bstride = s.bstride;
+  p.batch = s.batch;
+  p.min_distance = q.min_distance;
+  p.threshold_rel = q.threshold_rel;
+  p.idx1 = w.f.idx1;
+  p.v1 = w.f.v1;
+  p.zero_is_peak = w.f.zero_is_peak;
+  p.skipmask = w.f.skipmask;
+  p.cand_count = w.f.cand_count;
+  p.cand_val = w.f.cand_val;
+  p.cand_idx = w.f.cand_idx;
+  p.bitmap = w.f.bitmap;
+  p.group = w.f.group;
+  p.bitmap_words = w.f.bitmap_words;
   p.smax = w.smax;
   p.best = w.best;
   p.out = out;
-  if (!first_pass_done) {
-    // smax_done: the producer of the surfaces already left their maxima in
-    // w.smax (and the per-batch state was cleared before it ran)
-    if (!smax_done)
-      SFM_HIP_CHECK(hipMemsetAsync(ws_base + w.zero_from, 0, w.zero_bytes, st));
-    if (sn >= (1LL << 18) || smax_done) {
+  p.blk_rows = sfm::kMaskedBlkRows;
+  p.blk_n = (s.S[1] + sfm::kMaskedBlkRows - 1) / sfm::kMaskedBlkRows;
+  return p;
+}
+
+// What the producer of the surfaces has already done for the peak search.
+struct PeakDone {
+  bool first_pass;  // the whole first pass
+  bool smax;        // the surface maxima are in PeakWs::smax
+  bool nans;        // not done, asked for: the NaN-propagating surface maximum
+};
+
+int run_peaks(const PeakArgs& p, const PeakDone& done, const PeakWs& w, hipStream_t st) {
+  const int batch = p.batch;
+  if (!done.first_pass) {
+    if (!done.smax)
+      if (int rc = clear_peak_state(w, st)) return rc;
+    if (p.Sn >= (1LL << 18) || done.smax) {
       // large surfaces: ~32 K elements per workgroup
-      const long long rows = (long long)S[0] * S[1];
+      const long long rows = (long long)p.S[0] * p.S[1];
       const int chunks = static_cast<int>(std::min<long long>(
-          std::min<long long>(rows, 1024), std::max<long long>(1, sn >> 15)));
-      if (!smax_done) {
-        if (nans)
+          std::min<long long>(rows, 1024), std::max<long long>(1, p.Sn >> 15)));
+      if (!done.smax) {
+        if (done.nans)
           hipLaunchKernelGGL(peaks_max_kernel<true>, dim3(chunks, batch), dim3(kBlock), 0, st, p);
         else
           hipLaunchKernelGGL(peaks_max_kernel<false>, dim3(chunks, batch), dim3(kBlock), 0, st, p);
@@ -1173,7 +1193,7 @@ int run_peaks(const PeakWs& w, char* ws_base, const float* surf, int pitch,
         hipLaunchKernelGGL(peaks_scan_kernel, dim3(chunks, batch), dim3(kBlock), 0, st, p);
       hipLaunchKernelGGL(peaks_first_finish_kernel, dim3((batch + kBlock - 1) / kBlock),
                          dim3(kBlock), 0, st, p);
-    } else if (nans) {
+    } else if (done.nans) {
       hipLaunchKernelGGL(peaks_first_kernel<true>, dim3(batch), dim3(kBlock), 0, st, p);
     } else {
       hipLaunchKernelGGL(peaks_first_kernel<false>, dim3(batch), dim3(kBlock), 0, st, p);
@@ -1188,6 +1208,80 @@ int run_peaks(const PeakWs& w, char* ws_base, const float* surf, int pitch,
 // ---------------------------------------------------------------------------
 // batch driver
 // ---------------------------------------------------------------------------
+enum class Path { Direct, Fft, Mfma, MfmaMasked };
+enum class Entry { Size, Surface, Peaks };
+
+// The masked matrix-core path takes kMaskedGroups groups per round of launches:
+// its product surfaces are 4 GB per 1024 patches of 160^2 (SFM_MASKED_GROUPS).
+constexpr int kMaskedGroups = 8;
+
+// Everything an entry call decides before it launches (DESIGN.md has the table);
+// built once by make_plan, shared by the sizing and by every round of the run.
+struct XcorrPlan {
+  const SfmXcorrDesc* d;
+  Geo g;
+  Path path;
+  bool mfma, masked;        // mfma: either matrix-core path
+  bool peaks;               // Entry::Surface carves no peak state
+  int group;                // rows that share the batch-coupled state
+  long long round;          // rows per round of launches (a multiple of the group)
+  PeakDone done;            // what the producer of the surfaces does of the peak search
+  bool blkmax_ws;           // the producer writes block maxima (kBlkMaxN holds them)
+  bool blkmax, live_rows;   // the peak sweeps use them (SFM_MASKED_BLKMAX / _DEADROWS)
+};
+
+// `out`: the result pointer of the run entries.
+int make_plan(const SfmXcorrDesc* d, Entry e, const void* out, XcorrPlan* p) {
+  if (!d) return sfm::fail(SFM_ERR_INVALID, "desc is NULL");
+  if (d->batch < 1) return sfm::fail(SFM_ERR_INVALID, "batch must be >= 1");
+  if (d->group < 0) return sfm::fail(SFM_ERR_INVALID, "group must be >= 0");
+  if (!d->pre_image || !d->post_image || !d->pre_starts || !d->post_starts)
+    return sfm::fail(SFM_ERR_INVALID, "image / starts pointers must be set");
+  if (d->dtype != SFM_DTYPE_U8 && d->dtype != SFM_DTYPE_F32)
+    return sfm::fail(SFM_ERR_INVALID, "unsupported dtype tag %d", d->dtype);
+  if (d->method < SFM_XCORR_AUTO || d->method > SFM_XCORR_FFT)
+    return sfm::fail(SFM_ERR_INVALID, "unknown method %d", d->method);
+  const bool mfma = (d->method == SFM_XCORR_AUTO || d->method == SFM_XCORR_MFMA_I8) &&
+                    sfm::mfma_i8_eligible(d);
+  if (d->method == SFM_XCORR_MFMA_I8 && !mfma)
+    return sfm::fail(SFM_ERR_INVALID,
+                     "MFMA_I8 needs uint8 2-D images, post patches up to 160 wide and (un-masked) pre patches up to 320 wide");
+  if (e == Entry::Surface && !out) return sfm::fail(SFM_ERR_INVALID, "surface is NULL");
+  if (e == Entry::Peaks && !out) return sfm::fail(SFM_ERR_INVALID, "peaks is NULL");
+  if (int rc = make_geo(d, &p->g)) return rc;
+  p->d = d;
+  p->mfma = mfma;
+  p->masked = d->pre_mask || d->post_mask;
+  // FFT form: on request, or automatically for the patches the matrix-core
+  // kernel does not take once they are large enough (3-D, float, wide).
+  if (mfma)
+    p->path = p->masked ? Path::MfmaMasked : Path::Mfma;
+  else if (d->method == SFM_XCORR_FFT || (d->method == SFM_XCORR_AUTO && sfm::fft_preferred(d)))
+    p->path = Path::Fft;
+  else
+    p->path = Path::Direct;
+  // (the run leaves this check to fft_correlate, behind its workspace check)
+  if (e == Entry::Size && p->path == Path::Fft)
+    if (int rc = sfm::fft_check(d)) return rc;
+  p->peaks = e != Entry::Surface;
+  p->group = d->group > 0 && d->group < d->batch ? d->group : d->batch;
+  p->done = {p->path == Path::Mfma,
+             p->path == Path::MfmaMasked || (p->path == Path::Fft && !p->masked), false};
+  p->blkmax_ws = p->path == Path::MfmaMasked &&
+                 (p->g.S[1] + sfm::kMaskedBlkRows - 1) / sfm::kMaskedBlkRows <= kBlkMaxN;
+  p->blkmax = p->blkmax_ws && sfm::option_on("SFM_MASKED_BLKMAX");
+  p->live_rows = p->path == Path::MfmaMasked && sfm::option_on("SFM_MASKED_DEADROWS");
+  // The fused matrix-core path keeps the coupled state per group and takes any
+  // number of groups in one launch; the masked one keeps its maxima per group;
+  // every other path, and every masked surface call, runs group by group.
+  const bool whole = e == Entry::Surface ? !p->masked : p->path == Path::Mfma;
+  p->round = whole ? d->batch : p->group;
+  if (e != Entry::Surface && p->path == Path::MfmaMasked && p->group < d->batch)
+    p->round = std::min<long long>(
+        d->batch, p->round * std::max(1, sfm::option_int("SFM_MASKED_GROUPS", kMaskedGroups)));
+  return SFM_OK;
+}
+
 struct XcorrWs {
   float *a0, *b0, *va, *vb, *surface, *den, *ov;
   unsigned int* maxima;
@@ -1199,90 +1293,73 @@ struct XcorrWs {
   size_t bytes;
 };
 
-bool is_masked(const SfmXcorrDesc* d) { return d->pre_mask || d->post_mask; }
-
-bool use_mfma(const SfmXcorrDesc* d) {
-  if (d->method == SFM_XCORR_DIRECT || d->method == SFM_XCORR_FFT) return false;
-  return sfm::mfma_i8_eligible(d);
+// Rows `off` .. `off + rows` of the call.
+SfmXcorrDesc sub_desc(const XcorrPlan& p, long long off, long long rows) {
+  SfmXcorrDesc sub = *p.d;
+  sub.batch = static_cast<int>(rows);
+  sub.group = p.group;
+  sub.pre_starts += off * sub.ndim;
+  sub.post_starts += off * sub.ndim;
+  return sub;
 }
 
-// FFT form: on request, or automatically for the patches the matrix-core
-// kernel does not take once they are large enough (3-D, float, wide).
-bool use_fft(const SfmXcorrDesc* d) {
-  if (d->method == SFM_XCORR_FFT) return true;
-  if (d->method != SFM_XCORR_AUTO) return false;
-  return !sfm::mfma_i8_eligible(d) && sfm::fft_preferred(d);
-}
-
-XcorrWs carve_xcorr(const SfmXcorrDesc* d, const Geo& g, bool with_surface,
-                    bool with_peaks) {
-  sfm::Carver c(d->workspace);
+XcorrWs carve_xcorr(const XcorrPlan& p, long long rows, int group, void* base) {
+  SfmXcorrDesc q = *p.d;  // what the other units size by
+  q.batch = static_cast<int>(rows);
+  q.group = group;
+  const Geo& g = p.g;
+  sfm::Carver c(base);
   XcorrWs w;
   std::memset(&w, 0, sizeof(w));
-  const size_t B = d->batch;
-  const bool masked = is_masked(d);
-  if (use_mfma(d)) {
-    const size_t n = sfm::mfma_i8_workspace_bytes(d);
-    w.mfma = c.take<char>(n);
-    if (masked) {  // two maxima per reference batch of the call
-      const size_t rows = d->group > 0 && d->group < d->batch ? d->group : d->batch;
-      w.maxima = c.take<unsigned int>(2 * ((B + rows - 1) / rows));
+  const size_t B = rows;
+  w.srows = g.S[0] * g.S[1];
+  w.spitch = g.S[2];
+  if (p.mfma) {
+    w.mfma = c.take<char>(sfm::mfma_i8_workspace_bytes(&q));
+    if (p.masked) {  // two maxima per reference batch of the call
+      const size_t per = group > 0 && group < rows ? group : rows;
+      w.maxima = c.take<unsigned int>(2 * ((B + per - 1) / per));
     }
+    // The MFMA kernel stores whole 16 x 16 tiles: padded work surface.
+    sfm::mfma_i8_padded_dims(&q, &w.srows, &w.spitch);
   } else {
     w.a0 = c.take<float>(B * g.Pn);
     w.b0 = c.take<float>(B * g.Qn);
-    if (masked) {
+    if (p.masked) {
       w.va = c.take<float>(B * g.Pn);
       w.vb = c.take<float>(B * g.Qn);
       w.den = c.take<float>(B * g.Sn);
       w.ov = c.take<float>(B * g.Sn);
       w.maxima = c.take<unsigned int>(2);
     }
-    if (use_fft(d)) w.fft = c.take<char>(sfm::fft_workspace_bytes(d));
+    if (p.path == Path::Fft) w.fft = c.take<char>(sfm::fft_workspace_bytes(&q));
     if (std::max(g.Pn, g.Qn) >= (1LL << 16))
       w.gather_part = c.take<double>(B * 2 * kGatherChunks * 2);
   }
-  w.srows = g.S[0] * g.S[1];
-  w.spitch = g.S[2];
-  if (use_mfma(d)) {
-    // The MFMA kernel stores whole 16 x 16 tiles: padded work surface.
-    sfm::mfma_i8_padded_dims(d, &w.srows, &w.spitch);
-    with_surface = true;
-  }
-  if (with_surface) w.surface = c.take<float>(B * (size_t)w.srows * w.spitch);
-  if (with_peaks)
-    w.peaks = carve_peaks(c, d->batch, g.Sn, use_mfma(d) && !masked, d->group,
-                          use_mfma(d) && masked && (g.S[1] + sfm::kMaskedBlkRows - 1) / sfm::kMaskedBlkRows <= kBlkMaxN);
+  if (p.peaks || p.mfma)
+    w.surface = c.take<float>(B * (size_t)w.srows * w.spitch);
+  if (p.peaks)
+    w.peaks = carve_peaks(c, q.batch, g.Sn, p.done.first_pass, group, p.blkmax_ws);
   w.bytes = c.total();
   return w;
 }
 
-int check_desc(const SfmXcorrDesc* d) {
-  if (!d) return sfm::fail(SFM_ERR_INVALID, "desc is NULL");
-  if (d->batch < 1) return sfm::fail(SFM_ERR_INVALID, "batch must be >= 1");
-  if (d->group < 0) return sfm::fail(SFM_ERR_INVALID, "group must be >= 0");
-  if (!d->pre_image || !d->post_image || !d->pre_starts || !d->post_starts)
-    return sfm::fail(SFM_ERR_INVALID, "image / starts pointers must be set");
-  if (d->dtype != SFM_DTYPE_U8 && d->dtype != SFM_DTYPE_F32)
-    return sfm::fail(SFM_ERR_INVALID, "unsupported dtype tag %d", d->dtype);
-  if (d->method < SFM_XCORR_AUTO || d->method > SFM_XCORR_FFT)
-    return sfm::fail(SFM_ERR_INVALID, "unknown method %d", d->method);
-  if (d->method == SFM_XCORR_MFMA_I8 && !sfm::mfma_i8_eligible(d))
-    return sfm::fail(SFM_ERR_INVALID,
-                     "MFMA_I8 needs uint8 2-D images, post patches up to 160 wide and (un-masked) pre patches up to 320 wide");
-  return SFM_OK;
+template <typename T>
+void launch_gather(const GatherArgs* ga, int batch, bool own_mean, double* part,
+                   hipStream_t st) {
+  if (!part) {
+    hipLaunchKernelGGL(gather_kernel<T>, dim3(batch, 2), dim3(kBlock), 0, st, ga[0], ga[1]);
+    return;
+  }
+  const dim3 grid(kGatherChunks, batch, 2);
+  if (own_mean)
+    hipLaunchKernelGGL((gather_big_kernel<T, 0>), grid, dim3(kBlock), 0, st, ga[0], ga[1], part);
+  hipLaunchKernelGGL((gather_big_kernel<T, 1>), grid, dim3(kBlock), 0, st, ga[0], ga[1], part);
 }
 
-int compute_surface(const SfmXcorrDesc* d, const Geo& g, const XcorrWs& w,
-                    float* surface, const sfm::FusedPeaks* fused = nullptr,
-                    unsigned int* smax = nullptr) {
-  hipStream_t st = static_cast<hipStream_t>(d->stream);
-  const bool masked = is_masked(d);
-  if (use_mfma(d) && masked) {
-    // exact integer correlations on the matrix cores + Padfield assembly
-    return sfm::mfma_i8_masked(d, w.mfma, surface, w.maxima, smax, w.peaks.blkmax);
-  }
-  if (use_mfma(d)) return sfm::mfma_i8_surface(d, w.mfma, surface, fused);
+int gather_patches(const XcorrPlan& p, const SfmXcorrDesc* d, const XcorrWs& w,
+                   hipStream_t st) {
+  const Geo& g = p.g;
   GatherArgs ga[2];
   for (int k = 0; k < 2; ++k) {
     GatherArgs& a = ga[k];
@@ -1300,199 +1377,111 @@ int compute_surface(const SfmXcorrDesc* d, const Geo& g, const XcorrWs& w,
     a.use_mean = d->use_mean;
     a.mean = d->mean;
     a.out = k == 0 ? w.a0 : w.b0;
-    a.valid = masked ? (k == 0 ? w.va : w.vb) : nullptr;
+    a.valid = p.masked ? (k == 0 ? w.va : w.vb) : nullptr;
     a.pn = k == 0 ? g.Pn : g.Qn;
   }
-  if (w.gather_part) {
-    const dim3 grid(kGatherChunks, d->batch, 2);
-    if (d->dtype == SFM_DTYPE_U8) {
-      if (!d->use_mean)
-        hipLaunchKernelGGL((gather_big_kernel<unsigned char, 0>), grid, dim3(kBlock), 0,
-                           st, ga[0], ga[1], w.gather_part);
-      hipLaunchKernelGGL((gather_big_kernel<unsigned char, 1>), grid, dim3(kBlock), 0, st,
-                         ga[0], ga[1], w.gather_part);
-    } else {
-      if (!d->use_mean)
-        hipLaunchKernelGGL((gather_big_kernel<float, 0>), grid, dim3(kBlock), 0, st,
-                           ga[0], ga[1], w.gather_part);
-      hipLaunchKernelGGL((gather_big_kernel<float, 1>), grid, dim3(kBlock), 0, st, ga[0],
-                         ga[1], w.gather_part);
-    }
-  } else if (d->dtype == SFM_DTYPE_U8) {
-    hipLaunchKernelGGL(gather_kernel<unsigned char>, dim3(d->batch, 2),
-                       dim3(kBlock), 0, st, ga[0], ga[1]);
-  } else {
-    hipLaunchKernelGGL(gather_kernel<float>, dim3(d->batch, 2), dim3(kBlock), 0,
-                       st, ga[0], ga[1]);
-  }
+  if (d->dtype == SFM_DTYPE_U8)
+    launch_gather<unsigned char>(ga, d->batch, !d->use_mean, w.gather_part, st);
+  else
+    launch_gather<float>(ga, d->batch, !d->use_mean, w.gather_part, st);
   SFM_LAUNCH_CHECK();
-
-  CorrArgs c;
-  c.a = w.a0;
-  c.b = w.b0;
-  c.va = w.va;
-  c.vb = w.vb;
-  c.g = g;
-  c.out = surface;
-  c.den = w.den;
-  c.ov = w.ov;
-  c.maxima = w.maxima;
-  const long long gz = (long long)d->batch * g.S[0];
-  if (gz > 65535LL * 32768)
+  if ((long long)d->batch * g.S[0] > 65535LL * 32768)
     return sfm::fail(SFM_ERR_INVALID, "batch * S_z too large");
-  dim3 grid((g.S[2] + 63) / 64, (g.S[1] + 3) / 4, (unsigned)gz);
-  if (use_fft(d)) {
-    if (masked) SFM_HIP_CHECK(hipMemsetAsync(w.maxima, 0, 2 * sizeof(unsigned int), st));
-    sfm::prof_begin(sfm::kProfXcorr, st);
-    const int rc = sfm::fft_correlate(d, w.a0, w.b0, w.va, w.vb, surface, w.den, w.ov,
-                                      w.maxima, w.fft, masked ? nullptr : smax);
-    sfm::prof_end(sfm::kProfXcorr, st);
-    if (rc) return rc;
-    if (masked) {
-      const long long n = (long long)d->batch * g.Sn;
-      const int fg = (int)((n + kBlock - 1) / kBlock > 4096 ? 4096
-                                                             : (n + kBlock - 1) / kBlock);
-      hipLaunchKernelGGL(masked_finalize_kernel, dim3(fg), dim3(kBlock), 0, st,
-                         surface, w.den, w.ov, w.maxima, n);
-      SFM_LAUNCH_CHECK();
-    }
-    return SFM_OK;
-  }
-  if (masked) {
-    SFM_HIP_CHECK(hipMemsetAsync(w.maxima, 0, 2 * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(corr_direct_kernel<true>, grid, dim3(kBlock), 0, st, c);
-    SFM_LAUNCH_CHECK();
-    const long long n = (long long)d->batch * g.Sn;
-    const int fg = (int)((n + kBlock - 1) / kBlock > 4096 ? 4096
-                                                           : (n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(masked_finalize_kernel, dim3(fg), dim3(kBlock), 0, st,
-                       surface, w.den, w.ov, w.maxima, n);
-    SFM_LAUNCH_CHECK();
-  } else {
-    sfm::prof_begin(sfm::kProfXcorr, st);
-    hipLaunchKernelGGL(corr_direct_kernel<false>, grid, dim3(kBlock), 0, st, c);
-    sfm::prof_end(sfm::kProfXcorr, st);
-    SFM_LAUNCH_CHECK();
-  }
+  // the masked correlation accumulates the batch maxima for masked_finalize
+  if (p.masked) SFM_HIP_CHECK(hipMemsetAsync(w.maxima, 0, 2 * sizeof(unsigned int), st));
   return SFM_OK;
 }
 
-// Rows that share the reference's batch-coupled behaviours.
-int group_rows(const SfmXcorrDesc* d) {
-  return d->group > 0 && d->group < d->batch ? d->group : d->batch;
+// Padfield normalisation of a gathered (direct / FFT) surface.
+int masked_finalize(const XcorrWs& w, float* surface, long long n, hipStream_t st) {
+  const int grid = static_cast<int>(std::min<long long>((n + kBlock - 1) / kBlock, 4096));
+  hipLaunchKernelGGL(masked_finalize_kernel, dim3(grid), dim3(kBlock), 0, st, surface,
+                     w.den, w.ov, w.maxima, n);
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
 }
 
-// The fused MFMA path keeps the coupled state per group and takes any number
-// of groups in one launch; the masked matrix-core path keeps its maxima per group
-// and takes kMaskedGroups groups per round of launches (its product surfaces are
-// 4 GB per 1024 patches of 160^2; SFM_MASKED_GROUPS); every other path runs group
-// by group.
-constexpr int kMaskedGroups = 8;
-
-int masked_groups() {
-  const int n = sfm::option_int("SFM_MASKED_GROUPS", kMaskedGroups);
-  return n < 1 ? 1 : n;
-}
-
-bool one_launch(const SfmXcorrDesc* d) {
-  return group_rows(d) == d->batch || (use_mfma(d) && !is_masked(d));
-}
-
-// Rows of one round of launches of sfm_xcorr_peaks (a multiple of the group).
-long long call_rows(const SfmXcorrDesc* d) {
-  if (one_launch(d)) return d->batch;
-  const long long rows = group_rows(d);
-  if (use_mfma(d) && is_masked(d))
-    return std::min<long long>(d->batch, rows * masked_groups());
-  return rows;
-}
-
-SfmXcorrDesc sub_desc(const SfmXcorrDesc* d, int off, long long rows = 0) {
-  SfmXcorrDesc sub = *d;
-  if (rows <= 0) rows = group_rows(d);
-  sub.batch = static_cast<int>(d->batch - off < rows ? d->batch - off : rows);
-  sub.group = rows > group_rows(d) ? group_rows(d) : 0;
-  sub.pre_starts = d->pre_starts + (long long)off * d->ndim;
-  sub.post_starts = d->post_starts + (long long)off * d->ndim;
-  return sub;
-}
-
-int surface_one(const SfmXcorrDesc* d, const Geo& g, float* surface) {
-  XcorrWs w = carve_xcorr(d, g, false, false);
-  if (!d->workspace || d->workspace_bytes < w.bytes)
-    return sfm::fail(SFM_ERR_WORKSPACE, "xcorr workspace needs %zu bytes, got %zu",
-                     w.bytes, d->workspace_bytes);
-  if (use_mfma(d)) {
-    if (int rc = compute_surface(d, g, w, w.surface)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(d->stream);
-    hipLaunchKernelGGL(compact_surface_kernel, dim3(64, d->batch), dim3(kBlock), 0,
-                       st, w.surface, surface, g.S[1], g.S[2], w.srows, w.spitch);
-    SFM_LAUNCH_CHECK();
-    return SFM_OK;
+// `d`: the rows of this round (sub_desc).
+int compute_surface(const XcorrPlan& p, const SfmXcorrDesc* d, const XcorrWs& w,
+                    float* surface, const sfm::FusedPeaks* fused, unsigned int* smax) {
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  const Geo& g = p.g;
+  switch (p.path) {
+    case Path::MfmaMasked:
+      // exact integer correlations on the matrix cores + Padfield assembly
+      return sfm::mfma_i8_masked(d, w.mfma, surface, w.maxima, smax, w.peaks.blkmax);
+    case Path::Mfma:
+      return sfm::mfma_i8_surface(d, w.mfma, surface, fused);
+    case Path::Fft: {
+      if (int rc = gather_patches(p, d, w, st)) return rc;
+      sfm::prof_begin(sfm::kProfXcorr, st);
+      const int rc = sfm::fft_correlate(d, w.a0, w.b0, w.va, w.vb, surface, w.den, w.ov,
+                                        w.maxima, w.fft, smax);
+      sfm::prof_end(sfm::kProfXcorr, st);
+      if (rc) return rc;
+      break;
+    }
+    case Path::Direct: {
+      if (int rc = gather_patches(p, d, w, st)) return rc;
+      const CorrArgs c = {w.a0, w.b0, w.va, w.vb, g, surface, w.den, w.ov, w.maxima};
+      const dim3 grid((g.S[2] + 63) / 64, (g.S[1] + 3) / 4,
+                      (unsigned)((long long)d->batch * g.S[0]));  // bounded by gather_patches
+      if (p.masked) {
+        hipLaunchKernelGGL(corr_direct_kernel<true>, grid, dim3(kBlock), 0, st, c);
+      } else {
+        sfm::prof_begin(sfm::kProfXcorr, st);
+        hipLaunchKernelGGL(corr_direct_kernel<false>, grid, dim3(kBlock), 0, st, c);
+        sfm::prof_end(sfm::kProfXcorr, st);
+      }
+      SFM_LAUNCH_CHECK();
+      break;
+    }
   }
-  return compute_surface(d, g, w, surface);
+  return p.masked ? masked_finalize(w, surface, (long long)d->batch * g.Sn, st) : SFM_OK;
 }
 
-// SFM_MASKED_DEADROWS=0: the peak sweeps of the masked path read every row.
-bool live_rows_enabled() {
-  return sfm::option_on("SFM_MASKED_DEADROWS");
+int surface_round(const XcorrPlan& p, long long off, long long rows, float* surface) {
+  const SfmXcorrDesc sub = sub_desc(p, off, rows);
+  const XcorrWs w = carve_xcorr(p, rows, p.group, sub.workspace);
+  if (int rc = check_workspace("xcorr", sub.workspace, sub.workspace_bytes, w.bytes)) return rc;
+  if (!p.mfma) return compute_surface(p, &sub, w, surface, nullptr, nullptr);
+  if (int rc = compute_surface(p, &sub, w, w.surface, nullptr, nullptr)) return rc;
+  hipLaunchKernelGGL(compact_surface_kernel, dim3(64, sub.batch), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(sub.stream), w.surface, surface, p.g.S[1],
+                     p.g.S[2], w.srows, w.spitch);
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
 }
 
-// SFM_MASKED_BLKMAX=0: the peak sweep of the masked path reads every live row.
-bool blkmax_enabled() {
-  return sfm::option_on("SFM_MASKED_BLKMAX");
-}
-
-int peaks_one(const SfmXcorrDesc* d, const Geo& g, float* peaks) {
-  XcorrWs w = carve_xcorr(d, g, true, true);
-  if (!d->workspace || d->workspace_bytes < w.bytes)
-    return sfm::fail(SFM_ERR_WORKSPACE, "xcorr workspace needs %zu bytes, got %zu",
-                     w.bytes, d->workspace_bytes);
-  // With the MFMA kernel the first peak pass runs inside it, per finished
-  // surface; its per-batch state has to be cleared before the launch.
-  const bool fuse = use_mfma(d) && !is_masked(d);
-  sfm::FusedPeaks fp;
-  // masked matrix-core path and un-masked FFT form: the surface maxima come with
-  // the surfaces
-  const bool smax_pre = (use_mfma(d) && is_masked(d)) || (!use_mfma(d) && use_fft(d) && !is_masked(d));
-  if (fuse || smax_pre)
-    SFM_HIP_CHECK(hipMemsetAsync(static_cast<char*>(d->workspace) + w.peaks.zero_from,
-                                 0, w.peaks.zero_bytes,
-                                 static_cast<hipStream_t>(d->stream)));
-  if (fuse) {
-    fp.cand_cap = kCandCap;
-    fp.idx1 = w.peaks.idx1;
-    fp.v1 = w.peaks.v1;
-    fp.zero_is_peak = w.peaks.zero_is_peak;
-    fp.cand_count = w.peaks.cand_count;
-    fp.cand_val = w.peaks.cand_val;
-    fp.cand_idx = w.peaks.cand_idx;
-    fp.bitmap = w.peaks.bitmap;
-    fp.group = w.peaks.group;
-    fp.bitmap_words = w.peaks.bitmap_words;
-    fp.hot_cap = kHotCap;
-    fp.hot_count = w.peaks.hot_count;
-    fp.skipmask = w.peaks.skipmask;
-    fp.hot_val = w.peaks.hot_val;
-    fp.hot_idx = w.peaks.hot_idx;
-  }
-  if (int rc = compute_surface(d, g, w, w.surface, fuse ? &fp : nullptr,
-                               smax_pre ? w.peaks.smax : nullptr))
+int peaks_round(const XcorrPlan& p, long long off, long long rows, float* peaks) {
+  const SfmXcorrDesc sub = sub_desc(p, off, rows);
+  const Geo& g = p.g;
+  hipStream_t st = static_cast<hipStream_t>(sub.stream);
+  const XcorrWs w = carve_xcorr(p, rows, p.group, sub.workspace);
+  if (int rc = check_workspace("xcorr", sub.workspace, sub.workspace_bytes, w.bytes)) return rc;
+  const PeakDone& done = p.done;
+  if (done.first_pass || done.smax)
+    if (int rc = clear_peak_state(w.peaks, st)) return rc;
+  if (int rc = compute_surface(p, &sub, w, w.surface, done.first_pass ? &w.peaks.f : nullptr,
+                               done.smax ? w.peaks.smax : nullptr))
     return rc;
   float center[3];
   for (int i = 0; i < 3; ++i)
     center[i] = static_cast<float>((g.P[i] + g.Q[i]) / 2 - 1);
-  // masked matrix-core surfaces: rows below the overlap threshold are zeros (the
-  // assembly's second maximum, `maxima[1]`, is the batch maximum of the overlap)
-  const bool masked_mfma = use_mfma(d) && is_masked(d);
-  const int live_geo[3] = {g.P[1], g.Q[1], g.Q[2]};
-  return run_peaks(w.peaks, static_cast<char*>(d->workspace), w.surface,
-                   w.spitch, (long long)w.srows * w.spitch, d->ndim, g.S, g.Sn,
-                   d->batch, center, d->min_distance,
-                   d->threshold_rel, d->peak_radius, peaks,
-                   static_cast<hipStream_t>(d->stream), fuse, smax_pre,
-                   masked_mfma && live_rows_enabled() ? w.maxima + 1 : nullptr, live_geo,
-                   masked_mfma && w.peaks.blkmax && blkmax_enabled());
+  PeakArgs pa = make_peak_args(
+      w.peaks,
+      {w.surface, g.nd, g.S, g.Sn, w.spitch, (long long)w.srows * w.spitch, sub.batch},
+      sub, center, peaks);
+  if (p.path == Path::MfmaMasked) {
+    // rows below the overlap threshold are zeros (the assembly's second maximum,
+    // `maxima[1]`, is the batch maximum of the overlap)
+    if (p.live_rows) pa.live_ovmax = w.maxima + 1;
+    pa.live_py = g.P[1];
+    pa.live_qy = g.Q[1];
+    pa.live_qx = g.Q[2];
+    if (p.blkmax) pa.blkmax = w.peaks.blkmax;
+  }
+  return run_peaks(pa, done, w.peaks, st);
 }
 
 }  // namespace
@@ -1500,45 +1489,29 @@ int peaks_one(const SfmXcorrDesc* d, const Geo& g, float* peaks) {
 extern "C" {
 
 size_t sfm_xcorr_workspace_bytes(const SfmXcorrDesc* d) {
-  if (check_desc(d) != SFM_OK) return 0;
-  Geo g;
-  if (make_geo(d, &g) != SFM_OK) return 0;
-  if (use_fft(d) && sfm::fft_check(d) != SFM_OK) return 0;   // message in sfm_last_error
-  SfmXcorrDesc tmp = *d;
-  tmp.workspace = nullptr;
-  if (!one_launch(d)) {  // run group by group: scratch for one round of launches
-    const long long rows = call_rows(d);
-    tmp.batch = static_cast<int>(rows);
-    tmp.group = rows > group_rows(d) ? group_rows(d) : 0;
-  }
-  return carve_xcorr(&tmp, g, true, true).bytes;
+  XcorrPlan p;
+  if (make_plan(d, Entry::Size, nullptr, &p) != SFM_OK) return 0;  // message in sfm_last_error
+  return carve_xcorr(p, p.round, p.group, nullptr).bytes;
 }
 
 int sfm_xcorr_surface(const SfmXcorrDesc* d, float* surface) {
-  if (int rc = check_desc(d)) return rc;
-  if (!surface) return sfm::fail(SFM_ERR_INVALID, "surface is NULL");
-  Geo g;
-  if (int rc = make_geo(d, &g)) return rc;
-  if (!is_masked(d) || group_rows(d) == d->batch) return surface_one(d, g, surface);
+  XcorrPlan p;
+  if (int rc = make_plan(d, Entry::Surface, surface, &p)) return rc;
   // masked surfaces are normalised with maxima over their reference batch
-  for (int off = 0; off < d->batch; off += group_rows(d)) {
-    const SfmXcorrDesc sub = sub_desc(d, off);
-    if (int rc = surface_one(&sub, g, surface + (long long)off * g.Sn)) return rc;
-  }
+  for (long long off = 0; off < d->batch; off += p.round)
+    if (int rc = surface_round(p, off, std::min<long long>(p.round, d->batch - off),
+                               surface + off * p.g.Sn))
+      return rc;
   return SFM_OK;
 }
 
 int sfm_xcorr_peaks(const SfmXcorrDesc* d, float* peaks) {
-  if (int rc = check_desc(d)) return rc;
-  if (!peaks) return sfm::fail(SFM_ERR_INVALID, "peaks is NULL");
-  Geo g;
-  if (int rc = make_geo(d, &g)) return rc;
-  if (one_launch(d)) return peaks_one(d, g, peaks);
-  const long long rows = call_rows(d);
-  for (long long off = 0; off < d->batch; off += rows) {
-    const SfmXcorrDesc sub = sub_desc(d, static_cast<int>(off), rows);
-    if (int rc = peaks_one(&sub, g, peaks + off * (d->ndim + 2))) return rc;
-  }
+  XcorrPlan p;
+  if (int rc = make_plan(d, Entry::Peaks, peaks, &p)) return rc;
+  for (long long off = 0; off < d->batch; off += p.round)
+    if (int rc = peaks_round(p, off, std::min<long long>(p.round, d->batch - off),
+                             peaks + off * (p.g.nd + 2)))
+      return rc;
   return SFM_OK;
 }
 
@@ -1619,18 +1592,16 @@ int sfm_peaks(const SfmPeaksDesc* d, float* peaks) {
     if (d->peak_radius[i] < 0)
       return sfm::fail(SFM_ERR_INVALID, "peak_radius must be >= 0, got %d", d->peak_radius[i]);
   sfm::Carver c(d->workspace);
-  PeakWs w = carve_peaks(c, d->batch, sn);
-  if (!d->workspace || d->workspace_bytes < w.bytes)
-    return sfm::fail(SFM_ERR_WORKSPACE, "peaks workspace needs %zu bytes, got %zu",
-                     w.bytes, d->workspace_bytes);
+  const PeakWs w = carve_peaks(c, d->batch, sn);
+  if (int rc = check_workspace("peaks", d->workspace, d->workspace_bytes, w.bytes)) return rc;
+  const PeakArgs p = make_peak_args(
+      w, {d->surface, d->ndim, d->shape, sn, d->shape[2], sn, d->batch}, *d,
+      d->center_offset, peaks);
   // caller-supplied surfaces may hold NaN: the only entry that asks for the
   // NaN-propagating surface maximum
-  return run_peaks(w, static_cast<char*>(d->workspace), d->surface, d->shape[2],
-                   sn, d->ndim, d->shape, sn, d->batch, d->center_offset,
-                   d->min_distance,
-                   d->threshold_rel, d->peak_radius, peaks,
-                   static_cast<hipStream_t>(d->stream), false, false, nullptr, nullptr,
-                   false, true);
+  PeakDone done = {};
+  done.nans = true;
+  return run_peaks(p, done, w, static_cast<hipStream_t>(d->stream));
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@ from __future__ import annotations
 import collections.abc
 import ctypes as C
 import itertools
+import os
 import threading
 from typing import Callable, Iterator, Sequence, TypeVar
 
@@ -174,23 +175,7 @@ def _make_desc(res: _Resident, patch_size, post_patch_size, mean, min_distance,
 # workspace -- sized for the 288 GB of an MI355X): every launch ends with a
 # tail in which the CUs run dry one by one (the slower workgroup of a CU needs
 # ~400 us per patch), so 1 launch instead of 10 is worth 3-4 % (22.8 vs 23.7 ms).
-import os as _os
-LAUNCH_PATCHES = int(_os.environ.get('SFM_LAUNCH_PATCHES', '45056'))
-# Alternate consecutive calls between two streams (tail filling of the
-# persistent correlation kernel by the next call's prep kernel).
-OVERLAP_CALLS = False  # measured gain ~1 %: opt-in
-_SIDE_STREAMS = {}
-_SIDE_LOCK = threading.Lock()
-
-
-def _side_stream(dev) -> torch.cuda.Stream:
-  key = (torch.device(dev).index, threading.get_ident())
-  with _SIDE_LOCK:
-    if key not in _SIDE_STREAMS:
-      _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _SIDE_STREAMS[key]
-
-
+LAUNCH_PATCHES = int(os.environ.get('SFM_LAUNCH_PATCHES', '45056'))
 _FITTED = {}              # (device index, fraction) -> largest workspace that passed the budget check
 WORKSPACE_FRACTION = 0.6  # of the HBM that is free when a call is planned
 SMALL_WORKSPACE = 1 << 30  # calls below this are not checked against the budget
@@ -204,28 +189,17 @@ def _workspace_budget(dev) -> int:
   return int(WORKSPACE_FRACTION * (free + max(cached, 0)))
 
 
-def _run_batches_dev(res: _Resident, desc: _abi.SfmXcorrDesc, starts: torch.Tensor,
-                     batch_size: int, progress_fn=None) -> torch.Tensor:
-  """Enqueues every batch; `starts` is the device tensor [2, n, dim] of pre /
-  post start coordinates.  Returns the device peaks [n, dim + 2]."""
+def _fitted_key(dev):
+  return (torch.device(dev).index, WORKSPACE_FRACTION)
+
+
+def _size_call(desc: _abi.SfmXcorrDesc, batch_size: int, per_call: int, dev):
+  """(reference batches per C call, workspace bytes of such a call), at most
+  `per_call` batches.  The workspace grows with patches x surface area (26 GB for
+  a whole 8192^2 pair of 160^2 patches), so the call size is halved until its
+  workspace fits a fraction of the memory that is free right now (other ranks /
+  threads / jobs may share the GPU)."""
   lib = _abi.load()
-  nd = res.ndim
-  n = starts.shape[1]
-  assert n % batch_size == 0
-  n_batches = n // batch_size
-  peaks = torch.empty((n, nd + 2), dtype=torch.float32, device=res.dev)
-  # One C call carries several reference batches (`group` rows each keep the
-  # batch-coupled behaviours): fewer, larger launches fill the chip even when
-  # the reference batch is small.
-  per_call = min(max(1, LAUNCH_PATCHES // batch_size), n_batches)
-  desc.group = batch_size
-  desc.pre_starts = starts.data_ptr()
-  desc.post_starts = starts.data_ptr()
-  n_lanes = 2 if OVERLAP_CALLS else 1
-  # LAUNCH_PATCHES is an upper bound only: the workspace grows with patches x
-  # surface area (26 GB for a whole 8192^2 pair of 160^2 patches), so the call
-  # size is halved until every lane's workspace fits a fraction of the memory
-  # that is free right now (other ranks / threads / jobs may share the GPU).
   budget = None
   while True:
     desc.batch = per_call * batch_size
@@ -234,72 +208,66 @@ def _run_batches_dev(res: _Resident, desc: _abi.SfmXcorrDesc, starts: torch.Tens
       _abi.check(-1)
     # (the allocator statistics behind the budget cost 0.2 ms: asked for only
     # when a call wants more than SMALL_WORKSPACE)
-    if per_call == 1 or need * n_lanes <= SMALL_WORKSPACE:
-      break
+    if per_call == 1 or need <= SMALL_WORKSPACE:
+      return per_call, need
     # (nor when a workspace of at least this size passed the check on this device
     # before: the production loop asks for the same bytes section after section,
     # and torch's caching allocator still holds the block)
-    dev_key = (torch.device(res.dev).index, WORKSPACE_FRACTION)
-    if need * n_lanes <= _FITTED.get(dev_key, 0):
-      break
+    if need <= _FITTED.get(_fitted_key(dev), 0):
+      return per_call, need
     if budget is None:
-      budget = _workspace_budget(res.dev)
-    if need * n_lanes <= budget:
-      _FITTED[dev_key] = max(_FITTED.get(dev_key, 0), need * n_lanes)
-      break
-    per_call = max(1, per_call // 2)
-  row_bytes = batch_size * nd * 4
-  it = iter(range(n_batches) if progress_fn is None else progress_fn)
-  # Consecutive calls alternate between the current stream and a side stream
-  # (each with its own workspace): the hardware then fills the tail of one
-  # call's correlation kernel -- workgroups retiring one by one -- with the
-  # prep kernel and the first workgroups of the next call.
-  main = torch.cuda.current_stream(res.dev)
+      budget = _workspace_budget(dev)
+    if need <= budget:
+      _FITTED[_fitted_key(dev)] = max(_FITTED.get(_fitted_key(dev), 0), need)
+      return per_call, need
+    per_call //= 2
+
+
+def _run_batches_dev(res: _Resident, desc: _abi.SfmXcorrDesc, starts: torch.Tensor,
+                     batch_size: int, progress_fn=None) -> torch.Tensor:
+  """Enqueues every batch on the current stream; `starts` is the device tensor
+  [2, n, dim] of pre / post start coordinates.  Returns the device peaks
+  [n, dim + 2]."""
+  lib = _abi.load()
+  nd = res.ndim
+  n = starts.shape[1]
+  assert n % batch_size == 0
+  n_batches = n // batch_size
+  peaks = torch.empty((n, nd + 2), dtype=torch.float32, device=res.dev)
+  # One C call carries several reference batches (`group` rows each keep the
+  # batch-coupled behaviours): fewer, larger launches fill the chip even when
+  # the reference batch is small.  LAUNCH_PATCHES is an upper bound only.
+  desc.group = batch_size
+  desc.pre_starts = starts.data_ptr()
+  desc.post_starts = starts.data_ptr()
+  per_call = min(max(1, LAUNCH_PATCHES // batch_size), n_batches)
   while True:
+    per_call, need = _size_call(desc, batch_size, per_call, res.dev)
     try:
-      lanes = [(main, _dev.workspace(need, res.dev))]
+      ws = _dev.workspace(need, res.dev)
       break
     except torch.OutOfMemoryError:
       # a size that passed the budget earlier (_FITTED) no longer fits: memory
       # pressure grew or the cached block was released.  Forget it and go on
       # with smaller calls -- the field is the same (ADVICE r4).
-      _FITTED.pop((torch.device(res.dev).index, WORKSPACE_FRACTION), None)
+      _FITTED.pop(_fitted_key(res.dev), None)
       if per_call == 1:
         raise
-      per_call = max(1, per_call // 2)
-      desc.batch = per_call * batch_size
-      need = lib.sfm_xcorr_workspace_bytes(C.byref(desc))
-      if need == 0:
-        _abi.check(-1)
-  n_calls = (n_batches + per_call - 1) // per_call
-  if n_calls > 1 and OVERLAP_CALLS:
-    # the second lane is an optimisation: under memory pressure the calls simply stay on
-    # one stream
-    try:
-      side_ws = _dev.workspace(need, res.dev)
-    except torch.OutOfMemoryError:
-      side_ws = None
-    if side_ws is not None:
-      side = _side_stream(res.dev)
-      side.wait_stream(main)
-      lanes.append((side, side_ws))
-  for ci, bi in enumerate(range(0, n_batches, per_call)):
-    stream, ws = lanes[ci % len(lanes)]
+      per_call //= 2
+  desc.workspace = ws.data_ptr()
+  desc.workspace_bytes = ws.numel()
+  desc.stream = torch.cuda.current_stream(res.dev).cuda_stream
+  row_bytes = batch_size * nd * 4
+  it = iter(range(n_batches) if progress_fn is None else progress_fn)
+  for bi in range(0, n_batches, per_call):
     nb = min(per_call, n_batches - bi)
     desc.batch = nb * batch_size
-    desc.workspace = ws.data_ptr()
-    desc.workspace_bytes = ws.numel()
-    desc.stream = stream.cuda_stream
     desc.pre_starts = starts.data_ptr() + bi * row_bytes
     desc.post_starts = starts.data_ptr() + (n_batches + bi) * row_bytes
     out_ptr = peaks.data_ptr() + bi * batch_size * (nd + 2) * 4
     _abi.check(lib.sfm_xcorr_peaks(C.byref(desc), out_ptr))
     for _ in range(nb):
       next(it, None)
-  for stream, ws in lanes[1:]:
-    main.wait_stream(stream)
-    ws.record_stream(stream)
-  desc.stream = main.cuda_stream
   return peaks
 
 

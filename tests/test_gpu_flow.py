@@ -509,6 +509,8 @@ def test_mask_patch_counts_match_summed_area_table(gpu, shape, patch, step):
 @pytest.mark.parametrize('method,masked,dtype', [
     (0, False, np.uint8), (1, False, np.uint8), (0, True, np.uint8),
     (0, False, np.float32),
+    # FFT form: calls run group by group; un-masked it delivers the surface maxima
+    (3, False, np.float32), (3, True, np.float32),
 ])
 def test_many_batches_per_call_equal_batch_by_batch(gpu, monkeypatch, method,
                                                     masked, dtype):
