@@ -81,6 +81,9 @@ int sfm_device_count(int* count);
  *   SFM_MFMA_NARROW=n     lazy path: widest in-flight narrowing of a row loop (outer column
  *                         tiles dropped once proved cold; default: down to the four
  *                         central tiles; 0: never)
+ *   SFM_MFMA_RUN=n        same-size correlation launches: consecutive patches a workgroup takes
+ *                         per ticket of the patch queue (default 8; the end of a batch always
+ *                         goes out one patch at a time; 1: one patch per ticket throughout)
  *   SFM_MFMA_LAZYG=0      the prep kernel writes the whole correction table (default, pruned
  *                         flow launches: the finishing tiles build their 16 rows; the prep pass
  *                         then keeps no patch in LDS)
@@ -90,6 +93,8 @@ int sfm_device_count(int* count);
  *   SFM_MFMA_TOUCH_ALL=1  lazy path: pull a patch's whole correction table into L2
  *   SFM_MFMA_EXACT=0      run-time instead of compile-time column geometry
  *   SFM_MFMA_QUEUE=0      static instead of dynamic patch queue
+ *   SFM_MFMA_RUN_TAIL=n   patch queue: n x grid patches at the end of a batch go out one at a
+ *                         time (default 8)
  *   SFM_MFMA_PRIO=n       wave priority experiment (0..3)
  *   SFM_MFMA_MAX_WG_PER_CU=n   occupancy cap of the correlation kernel
  *   SFM_MASKED_FAST=0     masked patches always take all eight passes

@@ -125,6 +125,10 @@ constexpr int kBoundRows = 256;    // patch rows the prep kernel keeps energies 
 // (< 2^31 for every patch the matrix path takes); k <= 63, i.e. rows <= kEarlyRows
 constexpr int kRowPre = 128;
 constexpr int kEarlyRows = 252;
+// Measurement build: run statistics of a launch in the free words behind the queue head --
+// [1] waves finished; then (first patch of a run, inside a run) pairs: [2], [3] patches,
+// [4], [5] redone tiles, [6], [7] patches whose seed block was the block of their maximum.
+constexpr int kRunStatWords = 7;
 
 struct PatchParams {  // written by the prep kernel, one per patch
   int y0[2], x0[2];   // clamped patch origin in the image (pre, post)
@@ -240,6 +244,10 @@ struct MfmaArgs {
   long long s_stride; // padded surface: floats per patch = 16 * NP * sx_pitch
   // dynamic patch queue (NULL: static striding over the workgroups)
   int* work_counter;
+  // Queue ticket t -> patches (launch_one): tickets below n_runs are the run of `run`
+  // consecutive patches from t * run, later ones the single patch run_end + (t - n_runs);
+  // run_end = n_runs * run.  (run = 1, n_runs = run_end = 0: ticket t is patch t.)
+  int run, n_runs, run_end;
   // shader-clock probe: workgroup 0 leaves (core cycles, 10 ns wall ticks) of its
   // residency here (bench.py reports the sustained clock under this kernel);
   // clk[2]: dy tiles skipped by the pruning (low word) / drawn (high word), whole
@@ -277,12 +285,20 @@ __device__ __forceinline__ unsigned load_u32_guarded(const unsigned* base,
   return (idx >= 0 && idx < n_words) ? base[idx] : 0u;
 }
 
+// The correlation kernel's patch queue starts at ticket 0 (every prep kernel, one thread).
+__device__ __forceinline__ void reset_patch_queue(const MfmaArgs& a) {
+  *a.work_counter = 0;
+#ifdef SFM_MFMA_TIMING
+  for (int k = 1; k <= kRunStatWords; ++k) a.work_counter[k] = 0;  // run statistics
+#endif
+}
+
 // ---------------------------------------------------------------------------
 // prep: patch statistics, integer centre, integral image
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kThreads) mfma_prep_kernel(MfmaArgs a) {
   if (a.work_counter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
-    *a.work_counter = 0;  // the correlation kernel's patch queue
+    reset_patch_queue(a);
   if (a.clk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     a.clk[2] = a.clk[3] = a.clk[4] = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -415,7 +431,7 @@ typedef int v4i_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
 __global__ void __launch_bounds__(64 * kWidePrepWaves) mfma_prep_wide_kernel(MfmaArgs a) {
   if (a.work_counter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
-    *a.work_counter = 0;  // the correlation kernel's patch queue
+    reset_patch_queue(a);
   if (a.clk && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     a.clk[2] = a.clk[3] = a.clk[4] = 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1398,7 +1414,7 @@ template <bool LAZY>
 __global__ void __launch_bounds__(64 * kPrepWavesAlone, LAZY ? kPrepLazyWavesPerSimd : 1)
 mfma_prep_same_kernel(MfmaArgs a) {
   if (a.work_counter && blockIdx.x == 0 && threadIdx.x == 0)
-    *a.work_counter = 0;  // the correlation kernel's patch queue
+    reset_patch_queue(a);
   if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) a.clk[2] = a.clk[3] = a.clk[4] = 0;  // tile counts
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ PrepTables<kPrepWavesAlone, kBoundRows, LAZY> tables;
@@ -2603,14 +2619,28 @@ __global__ void __launch_bounds__(kThreads) mfma_first_peak_kernel(MfmaArgs a) {
   wave_first_peak(a, b, a.surface + b * a.s_stride, a.S[0], a.S[1], &s_cand[wave]);
 }
 
-// Next patch of this workgroup; called by all threads at the end of a patch.
-__device__ __forceinline__ int next_patch(const MfmaArgs& a, int b, int* next_lds) {
+// First patch of queue ticket t (see MfmaArgs::run).
+__device__ __forceinline__ int ticket_patch(const MfmaArgs& a, int t) {
+  return t < a.n_runs ? t * a.run : a.run_end + (t - a.n_runs);
+}
+
+// Next patch of this workgroup; called by all threads at the end of a patch.  `left`:
+// patches of the workgroup's run after b (wave-uniform).  Inside a run the next patch is
+// the next index: no barrier, no atomic.
+__device__ __forceinline__ int next_patch(const MfmaArgs& a, int b, int* next_lds, int& left) {
   if (!a.work_counter) return b + gridDim.x;
+  if (left > 0) {
+    --left;
+    return b + 1;
+  }
   __syncthreads();
-  if (threadIdx.x == 0) *next_lds = gridDim.x + atomicAdd(a.work_counter, 1);
+  if (threadIdx.x == 0)
+    *next_lds = ticket_patch(a, gridDim.x + atomicAdd(a.work_counter, 1));
   __syncthreads();
   // wave-uniform: keeps every per-patch base address in scalar registers
-  return __builtin_amdgcn_readfirstlane(*next_lds);
+  const int item = __builtin_amdgcn_readfirstlane(*next_lds);
+  left = item < a.run_end ? a.run - 1 : 0;
+  return item;
 }
 
 template <int NCA, int NCE, int MODE>
@@ -2687,6 +2717,7 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
   const long long wstart = wall_clock64();
   const long long cstart = clock64();
   long long tph[18] = {0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0}; long long tc = clock64(); int npat = 0;
+  int run_pat[2] = {0, 0}, run_redo[2] = {0, 0}, run_seed[2] = {0, 0};  // see kRunStatWords
 #define TICK(i) { long long tn = clock64(); tph[i] += tn - tc; tc = tn; }
 #else
 #define TICK(i)
@@ -2780,7 +2811,10 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
       const float m_lo = __int2float_rd(sm) - tb_lds[kBoundCorr];
       if (lane == 0 && m_lo > 0.f) atomicMax(pmax_lds, __float_as_int(m_lo));
   };
-  for (int item = blockIdx.x; item < n_items; item = next_patch(a, item, next_lds)) {
+  // The first assignment is ticket blockIdx.x.
+  const int item0 = ticket_patch(a, blockIdx.x);
+  int run_left = item0 < a.run_end ? a.run - 1 : 0;
+  for (int item = item0; item < n_items; item = next_patch(a, item, next_lds, run_left)) {
     int b = item;
     int plane0 = a.plane[0], plane1 = a.plane[1];
     if (RAW && a.list) {
@@ -2793,6 +2827,10 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
     }
 #ifdef SFM_MFMA_TIMING
     ++npat;
+    // (runs start at multiples of a.run below a.run_end; later patches are runs of one)
+    const int in_run = (item < a.run_end && item % a.run != 0) ? 1 : 0;
+    const int seed_pq = SAME && (a.prune || LAZY) ? *best_lds : -1;
+    ++run_pat[in_run];
 #endif
     TICK(7)
     float const_a = 0.f, const_b = 0.f;
@@ -3014,6 +3052,9 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
         old = __builtin_amdgcn_readfirstlane(old);
         if ((old >> p) & 1) continue;   // another wave took it
         forced = true;
+#ifdef SFM_MFMA_TIMING
+        ++run_redo[in_run];
+#endif
       }
       // (the tile's body is a block of its own: a `continue` inside it ends the tile; the
       // same code without the block gets another block layout and register allocation)
@@ -4348,6 +4389,9 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
       }
     }
     TICK(6)
+#ifdef SFM_MFMA_TIMING
+    if (seed_pq >= 0 && *best_lds == seed_pq) ++run_seed[in_run];
+#endif
   }
   if (a.clk && blockIdx.x == 0 && threadIdx.x == 0) {
     a.clk[0] = clock64() - probe_c0;
@@ -4367,6 +4411,23 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
     atomicAdd(reinterpret_cast<unsigned long long*>(a.clk + 4),
               static_cast<unsigned long long>(mfma_issued));
 #ifdef SFM_MFMA_TIMING
+  if (a.work_counter && lane == 0) {
+    // Run statistics of the launch; the wave that finishes last prints them.
+    int* rs = a.work_counter;
+    for (int k = 0; k < 2; ++k) {
+      if (wave == 0) atomicAdd(rs + 2 + k, run_pat[k]);
+      atomicAdd(rs + 4 + k, run_redo[k]);
+      if (wave == 0) atomicAdd(rs + 6 + k, run_seed[k]);
+    }
+    __threadfence();
+    if (atomicAdd(rs + 1, 1) == static_cast<int>(gridDim.x * (blockDim.x >> 6)) - 1) {
+      int v[6];
+      for (int k = 0; k < 6; ++k) v[k] = atomicAdd(rs + 2 + k, 0);
+      printf("RUNS run %d grid %d batch %d: patches head %d inside %d redone head %d inside %d "
+             "seed==peak head %d inside %d\n",
+             a.run, gridDim.x, a.batch, v[0], v[1], v[2], v[3], v[4], v[5]);
+    }
+  }
   if (lane == 0 && wave == 0) {
     // HW_REG_HW_ID (4): [11:8] CU, [12] SH, [15:13] SE; HW_REG_XCC_ID (20): [3:0]
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);
@@ -4489,6 +4550,36 @@ Ws carve_ws(const SfmXcorrDesc* d, void* base) {
   return w;
 }
 
+// How the patch queue hands out the batch to `grid` workgroups (MfmaArgs::run).  RUNS: the
+// same-size launches, whose workgroups carry predictions from patch to patch; the raw and
+// search-window launches keep one patch per ticket.
+//
+// A workgroup predicts the seed block, the need mask and the hot columns of a patch from its
+// previous one, so consecutive patches of a workgroup should be neighbours in the field: a
+// ticket is a run of kRun consecutive patches (SFM_MFMA_RUN=n; 1: one patch per ticket, the
+// order before runs existed).  The last kRunTail x grid patches go out one at a time, so that
+// the launch ends balanced (a run is kRun x ~120 us of a workgroup; SFM_MFMA_RUN_TAIL=n, a
+// measurement switch).  A batch below grid x run shrinks the run: nobody starts without work
+// while others hold runs.  8 / 8: measured, DESIGN_LOG.md "Runs".
+constexpr int kRun = 8;
+constexpr int kRunTail = 8;
+template <bool RUNS>
+void set_runs(int grid, MfmaArgs* ap) {
+  MfmaArgs& a = *ap;
+  a.run = 1;
+  a.n_runs = a.run_end = 0;
+  if (!RUNS || !a.work_counter || grid < 1) return;
+  const int want = std::min(std::max(sfm::option_int("SFM_MFMA_RUN", kRun), 1), 64);
+  a.run = std::max(std::min(want, a.batch / grid), 1);
+  if (a.run == 1) return;
+  const int tail_mult = std::max(sfm::measure_option_int("SFM_MFMA_RUN_TAIL", kRunTail), 0);
+  // (the first assignment of every workgroup stays a run)
+  const long long tail = std::min<long long>((long long)tail_mult * grid,
+                                             a.batch - (long long)grid * a.run);
+  a.n_runs = static_cast<int>((a.batch - tail) / a.run);
+  a.run_end = a.n_runs * a.run;
+}
+
 template <int NCA, int NCE, int MODE>
 int launch_one(const MfmaArgs& a, int grid, size_t lds, hipStream_t st) {
   // (search-window variants: eight waves per workgroup, see WIDE8 in the kernel)
@@ -4513,9 +4604,11 @@ int launch_one(const MfmaArgs& a, int grid, size_t lds, hipStream_t st) {
     const int g = sfm::option_int("SFM_MFMA_GRID", 0);
     if (g > 0) grid = std::min(grid, g);
   }
+  MfmaArgs ar = a;
+  set_runs<NCA <= 10 && MODE != kModeGeneral && MODE != kModeRaw>(grid, &ar);
   sfm::prof_begin(sfm::kProfXcorr, st);
   hipLaunchKernelGGL((xcorr_mfma_kernel<NCA, NCE, MODE>), dim3(grid),
-                     dim3(kThreadsV), lds, st, a);
+                     dim3(kThreadsV), lds, st, ar);
   sfm::prof_end(sfm::kProfXcorr, st);
   sfm::prof_clock(sfm::kProfXcorr, a.clk, st, 5);
   SFM_LAUNCH_CHECK();
