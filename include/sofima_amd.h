@@ -40,7 +40,8 @@ extern "C" {
                                    double thresholds; sfm_map_shift, sfm_map_extents,
                                    sfm_affine_map and sfm_warp_points were added
                                    without a bump: new entry points only, no
-                                   existing struct or call changed */
+                                   existing struct or call changed; likewise
+                                   sfm_prev_state and sfm_mask_irregular_f64 */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -443,6 +444,53 @@ typedef struct SfmMaskIrregularDesc {
  * [y, x] (1 = masked). */
 int sfm_mask_irregular(const SfmMaskIrregularDesc* desc, float* coord_map,
                        uint8_t* bad);
+/* The same test on a float64 map, not narrowed: the neighbour difference is
+ * taken in double, as np.diff does for a float64 map.  coord_map: device double
+ * [2, y, x], modified in place.  n_valid: device int32, written: the number of
+ * nodes that keep a component that is not NaN (0 <=> np.all(np.isnan(map))). */
+int sfm_mask_irregular_f64(const SfmMaskIrregularDesc* desc, double* coord_map,
+                           uint8_t* bad, int32_t* n_valid);
+
+/* ------------------------------------------------------------------------
+ * Reference positions of one section from several flows at once.
+ * Replaces the compute part of RelaxMesh.get_prev_state with compute_ref_mesh
+ * and compute_ref_mesh_multiz (processor/mesh.py:170-371): every flow is
+ * composed with the solved mesh of the section it was measured against
+ * (map_utils.compose_maps_fast, mode nearest, both maps at the same box start)
+ * and the composed vectors are averaged per node over the flows that gave a
+ * finite x component.  A 2-channel flow has one reference section.  A
+ * 3-channel flow picks its reference per node: channel 2 is compared for exact
+ * equality with delta_z[k]; a node that matches no entry (NaN, 0, a fraction,
+ * a section of another block) contributes NaN.  Sums are kept in double:
+ * NaN adds 0, +-inf adds +-FLT_MAX (2 channels: np.nan_to_num of the float32
+ * composed map) or +-DBL_MAX (3 channels: of the float64 array the reference
+ * collects the vectors in); a node without a finite vector is NaN.
+ * Which flows and sections take part is host logic
+ * (sofima_amd.processor_mesh.refs_for_section).
+ * ---------------------------------------------------------------------- */
+#define SFM_PREV_MAX_FLOWS 8
+#define SFM_PREV_MAX_REFS 16
+
+typedef struct SfmPrevFlow {
+  int32_t channels;             /* 2 or 3                                    */
+  int32_t n_refs;               /* 2 channels: 1; 3 channels: 0 to 16        */
+  const float* flow;            /* device, channel c at flow + c * flow_channel_stride, each [y, x] */
+  int64_t flow_channel_stride;  /* elements, >= y * x                        */
+  int64_t mesh_channel_stride;  /* elements between the x and y plane of a mesh[k] */
+  int32_t delta_z[SFM_PREV_MAX_REFS];   /* 3 channels: look-back offsets, none 0 */
+  const float* mesh[SFM_PREV_MAX_REFS]; /* device: x plane [y, x] of section z - delta_z[k] */
+} SfmPrevFlow;
+
+typedef struct SfmPrevStateDesc {
+  int32_t shape[2];             /* y, x                                      */
+  int32_t n_flows;              /* 1 to 8, averaged in this order            */
+  float stride[2];              /* y, x: compose_maps_fast's stride          */
+  SfmPrevFlow flows[SFM_PREV_MAX_FLOWS];
+  void* stream;
+} SfmPrevStateDesc;
+
+/* out: device double [2, y, x]; must not overlap any input. */
+int sfm_prev_state(const SfmPrevStateDesc* desc, double* out);
 
 /* ------------------------------------------------------------------------
  * Warping one image section by an inverse coordinate map.

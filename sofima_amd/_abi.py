@@ -329,6 +329,32 @@ class SfmTargetMeshDesc(C.Structure):
   ]
 
 
+PREV_MAX_FLOWS = 8
+PREV_MAX_REFS = 16
+
+
+class SfmPrevFlow(C.Structure):
+  _fields_ = [
+      ('channels', i32),
+      ('n_refs', i32),
+      ('flow', C.c_void_p),
+      ('flow_channel_stride', C.c_int64),
+      ('mesh_channel_stride', C.c_int64),
+      ('delta_z', i32 * PREV_MAX_REFS),
+      ('mesh', C.c_void_p * PREV_MAX_REFS),
+  ]
+
+
+class SfmPrevStateDesc(C.Structure):
+  _fields_ = [
+      ('shape', i32 * 2),
+      ('n_flows', i32),
+      ('stride', C.c_float * 2),
+      ('flows', SfmPrevFlow * PREV_MAX_FLOWS),
+      ('stream', C.c_void_p),
+  ]
+
+
 FORCE_SPRINGS = 0
 FORCE_TILE_MESH = 1
 FORCE_EXTERNAL = 2
@@ -465,6 +491,9 @@ SIGNATURES = {
     'sfm_invert_map': (C.c_int, [C.POINTER(SfmInvertMapDesc), C.c_void_p]),
     'sfm_mask_irregular': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,
                                      C.c_void_p]),
+    'sfm_mask_irregular_f64': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    'sfm_prev_state': (C.c_int, [C.POINTER(SfmPrevStateDesc), C.c_void_p]),
     'sfm_flow_starts': (C.c_int, [C.POINTER(SfmFlowStartsDesc)]),
     'sfm_flow_scatter': (C.c_int, [C.POINTER(SfmFlowScatterDesc)]),
     'sfm_warp_section': (C.c_int, [C.POINTER(SfmWarpDesc)]),

@@ -104,28 +104,33 @@ __global__ void __launch_bounds__(kBlock) clean_flow_kernel(CleanArgs a) {
   for (int c = 0; c < a.dim; ++c) a.out[c * n_vec + i] = bad ? NAN : v[c];
 }
 
+// T: element type of the map (float, or double for sfm_mask_irregular_f64)
+template <typename T>
 struct IrregArgs {
-  float* map;          // [2, Y, X]
+  T* map;              // [2, Y, X]
   unsigned char* bad;  // [Y, X]
+  int* n_valid;        // counting fill only
   int Y, X, iters;
   double sx, sy, lo_x, lo_y, hi_x, hi_y;
 };
 
 // bad before dilation (map_utils.py:768-775); out-of-range nodes are not bad.
-__device__ __forceinline__ bool irregular_at(const IrregArgs& a, int y, int x) {
+template <typename T>
+__device__ __forceinline__ bool irregular_at(const IrregArgs<T>& a, int y, int x) {
   if (y < 0 || y >= a.Y || x < 0 || x >= a.X) return false;
   const long long n = (long long)a.Y * a.X, i = (long long)y * a.X + x;
-  // np.diff in float32, padded with 0 at the far edge; the float64 stride
+  // np.diff in the map's type, padded with 0 at the far edge; the float64 stride
   // scalar promotes the sum, and the comparisons, to double (NumPy >= 2)
-  const double dx = static_cast<double>(x + 1 < a.X ? a.map[i + 1] - a.map[i] : 0.f) + a.sx;
+  const double dx = static_cast<double>(x + 1 < a.X ? a.map[i + 1] - a.map[i] : T(0)) + a.sx;
   const double dy =
-      static_cast<double>(y + 1 < a.Y ? a.map[n + i + a.X] - a.map[n + i] : 0.f) + a.sy;
+      static_cast<double>(y + 1 < a.Y ? a.map[n + i + a.X] - a.map[n + i] : T(0)) + a.sy;
   return dx < a.lo_x || dy < a.lo_y || dx > a.hi_x || dy > a.hi_y;
 }
 
 // `iters` dilations with the full 3 x 3 structure == OR over the square window
 // of radius `iters` (border value 0).
-__global__ void __launch_bounds__(kBlock) irregular_mark_kernel(IrregArgs a) {
+template <typename T>
+__global__ void __launch_bounds__(kBlock) irregular_mark_kernel(IrregArgs<T> a) {
   const long long n = (long long)a.Y * a.X;
   const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
   if (i >= n) return;
@@ -141,25 +146,34 @@ __global__ void __launch_bounds__(kBlock) irregular_mark_kernel(IrregArgs a) {
 }
 
 // Second launch: the NaN fill must not feed back into the differences above.
-__global__ void __launch_bounds__(kBlock) irregular_fill_kernel(IrregArgs a) {
+// COUNT: also add up the nodes that keep a component that is not NaN, one
+// atomic per wave.
+template <typename T, bool COUNT>
+__global__ void __launch_bounds__(kBlock) irregular_fill_kernel(IrregArgs<T> a) {
   const long long n = (long long)a.Y * a.X;
   const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
-  if (i >= n || !a.bad[i]) return;
-  a.map[i] = NAN;
-  a.map[n + i] = NAN;
+  const bool bad = i < n && a.bad[i];
+  if (bad) {
+    a.map[i] = NAN;
+    a.map[n + i] = NAN;
+  }
+  if (COUNT) {
+    const bool valid = i < n && !bad && !(isnan(a.map[i]) && isnan(a.map[n + i]));
+    const int cnt = __popcll(__ballot(valid));
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(a.n_valid, cnt);
+  }
 }
 
-}  // namespace
-
-extern "C" int sfm_mask_irregular(const SfmMaskIrregularDesc* d, float* coord_map,
-                                  uint8_t* bad) {
+template <typename T>
+int mask_irregular(const SfmMaskIrregularDesc* d, T* coord_map, uint8_t* bad, int* n_valid) {
   if (!d || !coord_map || !bad)
     return sfm::fail(SFM_ERR_INVALID, "mask_irregular: NULL argument");
   if (d->shape[0] < 1 || d->shape[1] < 1 || d->dilation_iters < 0)
     return sfm::fail(SFM_ERR_INVALID, "mask_irregular: bad shape / iterations");
-  IrregArgs a;
+  IrregArgs<T> a;
   a.map = coord_map;
   a.bad = bad;
+  a.n_valid = n_valid;
   a.Y = d->shape[0];
   a.X = d->shape[1];
   a.iters = d->dilation_iters;
@@ -172,10 +186,26 @@ extern "C" int sfm_mask_irregular(const SfmMaskIrregularDesc* d, float* coord_ma
   const long long n = (long long)a.Y * a.X;
   const unsigned grid = static_cast<unsigned>((n + kBlock - 1) / kBlock);
   hipStream_t st = static_cast<hipStream_t>(d->stream);
-  hipLaunchKernelGGL(irregular_mark_kernel, dim3(grid), dim3(kBlock), 0, st, a);
-  hipLaunchKernelGGL(irregular_fill_kernel, dim3(grid), dim3(kBlock), 0, st, a);
+  if (n_valid) SFM_HIP_CHECK(hipMemsetAsync(n_valid, 0, sizeof(int), st));
+  hipLaunchKernelGGL(irregular_mark_kernel<T>, dim3(grid), dim3(kBlock), 0, st, a);
+  // the float entry has no counter, the double entry always has one
+  constexpr bool kCount = sizeof(T) == sizeof(double);
+  hipLaunchKernelGGL((irregular_fill_kernel<T, kCount>), dim3(grid), dim3(kBlock), 0, st, a);
   SFM_LAUNCH_CHECK();
   return SFM_OK;
+}
+
+}  // namespace
+
+extern "C" int sfm_mask_irregular(const SfmMaskIrregularDesc* d, float* coord_map,
+                                  uint8_t* bad) {
+  return mask_irregular<float>(d, coord_map, bad, nullptr);
+}
+
+extern "C" int sfm_mask_irregular_f64(const SfmMaskIrregularDesc* d, double* coord_map,
+                                      uint8_t* bad, int32_t* n_valid) {
+  if (!n_valid) return sfm::fail(SFM_ERR_INVALID, "mask_irregular: NULL argument");
+  return mask_irregular<double>(d, coord_map, bad, n_valid);
 }
 
 // ---------------------------------------------------------------------------

@@ -65,6 +65,67 @@ __global__ void __launch_bounds__(kBlock) compose_kernel(ComposeArgs a) {
   }
 }
 
+// np.nan_to_num of a float32 / float64 value, widened: NaN -> 0, +-inf -> the
+// largest finite value of the type the reference holds the composed map in.
+__device__ __forceinline__ double nan_to_num_as(float v, bool as_f64) {
+  if (isnan(v)) return 0.0;
+  if (isinf(v)) {
+    const double big = as_f64 ? 1.7976931348623157e308 : 3.4028234663852886e38;
+    return v > 0.f ? big : -big;
+  }
+  return static_cast<double>(v);
+}
+
+// RelaxMesh.get_prev_state (processor/mesh.py:279-371) for one section: every
+// flow composed with the solved mesh of the section it was measured against
+// (compose_kernel's in-plane expression with both offsets 0, mode nearest),
+// then the per-node mean over the flows that gave a finite vector.  One thread
+// per node, lanes along x; the flow table is read through scalar loads.
+__global__ void __launch_bounds__(kBlock) prev_state_kernel(SfmPrevStateDesc d, double* out) {
+  const int Y = d.shape[0], X = d.shape[1];
+  const long long n = (long long)Y * X;
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int x = static_cast<int>(i % X), y = static_cast<int>(i / X);
+  const float st_y = d.stride[0], st_x = d.stride[1];
+  const float ref1x = static_cast<float>(x) * st_x;
+  const float ref1y = static_cast<float>(y) * st_y;
+  double sum_x = 0.0, sum_y = 0.0;
+  int count = 0;
+  for (int f = 0; f < d.n_flows; ++f) {
+    const SfmPrevFlow& fl = d.flows[f];
+    const float* mesh = nullptr;
+    if (fl.channels == 2) {
+      mesh = fl.mesh[0];
+    } else {
+      // exact equality with the look-back offset (processor/mesh.py:217); NaN,
+      // 0, fractions and offsets without a reference section match nothing
+      const float dz = fl.flow[2 * fl.flow_channel_stride + i];
+      for (int k = 0; k < fl.n_refs; ++k)
+        if (dz == static_cast<float>(fl.delta_z[k])) mesh = fl.mesh[k];
+    }
+    float cx = NAN, cy = NAN;
+    if (mesh) {
+      const float qx = (ref1x + fl.flow[i]) / st_x;
+      const float qy = (ref1y + fl.flow[fl.flow_channel_stride + i]) / st_y;
+      cx = sample2(plain(mesh), Y, X, qy, qx, false, 1, 0.f, st_x) - ref1x;
+      cy = sample2(plain(mesh + fl.mesh_channel_stride), Y, X, qy, qx, false, 0, 0.f, st_y) -
+           ref1y;
+    }
+    // the 3-channel path collects its vectors in a float64 array (:184), the
+    // 2-channel path hands on compose_maps_fast's float32 (:266)
+    const bool as_f64 = fl.channels == 3;
+    count += isfinite(cx) ? 1 : 0;
+    sum_x += nan_to_num_as(cx, as_f64);
+    sum_y += nan_to_num_as(cy, as_f64);
+  }
+  // count.astype(float32), 0 -> NaN, float64 / float32 (:369-371); a finite
+  // sum over NaN is the default quiet NaN, written as such
+  const double div = static_cast<double>(static_cast<float>(count));
+  out[i] = count ? sum_x / div : __builtin_nan("");
+  out[n + i] = count ? sum_y / div : __builtin_nan("");
+}
+
 struct TargetArgs {
   SfmTargetMeshDesc d;
   const float* x;
@@ -283,6 +344,41 @@ int sfm_compose_maps(const SfmComposeDesc* d, float* out) {
   const long long n1 = (long long)a.s1[0] * a.s1[1] * a.s1[2];
   hipStream_t st = static_cast<hipStream_t>(d->stream);
   hipLaunchKernelGGL(compose_kernel, dim3(grid_for(n1)), dim3(kBlock), 0, st, a);
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
+}
+
+int sfm_prev_state(const SfmPrevStateDesc* d, double* out) {
+  if (!d || !out) return sfm::fail(SFM_ERR_INVALID, "prev_state: NULL argument");
+  if (d->shape[0] < 1 || d->shape[1] < 1)
+    return sfm::fail(SFM_ERR_INVALID, "prev_state: bad shape");
+  if (d->n_flows < 1 || d->n_flows > SFM_PREV_MAX_FLOWS)
+    return sfm::fail(SFM_ERR_INVALID, "prev_state: 1 to 8 flows");
+  if (!(d->stride[0] > 0.f) || !(d->stride[1] > 0.f))
+    return sfm::fail(SFM_ERR_INVALID, "prev_state: stride must be positive");
+  const long long n = (long long)d->shape[0] * d->shape[1];
+  for (int f = 0; f < d->n_flows; ++f) {
+    const SfmPrevFlow& fl = d->flows[f];
+    if (fl.channels != 2 && fl.channels != 3)
+      return sfm::fail(SFM_ERR_INVALID, "prev_state: a flow has 2 or 3 channels");
+    if (!fl.flow || fl.flow_channel_stride < n)
+      return sfm::fail(SFM_ERR_INVALID, "prev_state: NULL flow or overlapping channel planes");
+    if (fl.channels == 2 ? fl.n_refs != 1 : (fl.n_refs < 0 || fl.n_refs > SFM_PREV_MAX_REFS))
+      return sfm::fail(SFM_ERR_INVALID,
+                       "prev_state: one reference per 2-channel flow, at most 16 per 3-channel flow");
+    if (fl.n_refs > 0 && fl.mesh_channel_stride < n)
+      return sfm::fail(SFM_ERR_INVALID, "prev_state: overlapping mesh planes");
+    for (int k = 0; k < fl.n_refs; ++k) {
+      if (!fl.mesh[k]) return sfm::fail(SFM_ERR_INVALID, "prev_state: NULL reference mesh");
+      if (fl.channels == 3 && fl.delta_z[k] == 0)
+        return sfm::fail(SFM_ERR_INVALID, "prev_state: look-back offset 0");
+    }
+  }
+  const long long grid = (n + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffffLL) return sfm::fail(SFM_ERR_INVALID, "prev_state: section too large");
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  hipLaunchKernelGGL(prev_state_kernel, dim3(static_cast<unsigned>(grid)), dim3(kBlock), 0, st,
+                     *d, out);
   SFM_LAUNCH_CHECK();
   return SFM_OK;
 }

@@ -23,7 +23,9 @@ __device__ __forceinline__ Axis make_axis(float q) {
   const float f = floorf(q);
   a.w_hi = q - f;
   a.w_lo = 1.0f - a.w_hi;
-  a.lo = static_cast<int>(f);
+  // q beyond the int range (or +-inf, whose weights are NaN): lo + 1 must not
+  // overflow, whichever way the compiler orders the clamps of the samplers
+  a.lo = static_cast<int>(fminf(fmaxf(f, -1073741824.f), 1073741824.f));
   return a;
 }
 

@@ -79,6 +79,18 @@ def compose_maps_fast(map1, start1: Sequence[float], stride1, map2,
   return DeviceArray(out)
 
 
+def _irregular_desc(shape, stride_x, stride_y, frac, max_frac, dilation_iters):
+  d = _abi.SfmMaskIrregularDesc()
+  d.shape = (C.c_int32 * 2)(int(shape[1]), int(shape[2]))
+  d.dilation_iters = int(dilation_iters)
+  frac, max_frac = float(frac), float(max_frac)
+  d.stride = (C.c_double * 2)(stride_x, stride_y)
+  d.min_dist = (C.c_double * 2)(frac * stride_x, frac * stride_y)
+  d.max_dist = (C.c_double * 2)(max_frac * stride_x, max_frac * stride_y)
+  d.stream = _dev.stream_ptr()
+  return d
+
+
 def mask_irregular(coord_map, stride: Sequence[float], frac: float,
                    max_frac: float | None = None,
                    dilation_iters: int = 1) -> np.ndarray:
@@ -109,14 +121,7 @@ def mask_irregular(coord_map, stride: Sequence[float], frac: float,
   dev = _dev.device()
   host = coord_map if isinstance(coord_map, np.ndarray) else None
   m = _dev.as_device_f32(coord_map, dev, copy=host is not None)
-  d = _abi.SfmMaskIrregularDesc()
-  d.shape = (C.c_int32 * 2)(int(shape[1]), int(shape[2]))
-  d.dilation_iters = int(dilation_iters)
-  frac, max_frac = float(frac), float(max_frac)
-  d.stride = (C.c_double * 2)(stride_x, stride_y)
-  d.min_dist = (C.c_double * 2)(frac * stride_x, frac * stride_y)
-  d.max_dist = (C.c_double * 2)(max_frac * stride_x, max_frac * stride_y)
-  d.stream = _dev.stream_ptr()
+  d = _irregular_desc(shape, stride_x, stride_y, frac, max_frac, dilation_iters)
   bad = torch.empty(tuple(shape[1:]), dtype=torch.uint8, device=dev)
   _abi.check(_abi.load().sfm_mask_irregular(C.byref(d), m.data_ptr(), bad.data_ptr()))
   bad_h = bad.cpu().numpy().astype(bool)
@@ -128,6 +133,32 @@ def mask_irregular(coord_map, stride: Sequence[float], frac: float,
     else:
       host[:, bad_h] = np.nan
   return bad_h
+
+
+def mask_irregular_f64(coord_map, stride: Sequence[float], frac: float,
+                       max_frac: float | None = None,
+                       dilation_iters: int = 1) -> tuple[torch.Tensor, torch.Tensor]:
+  """`mask_irregular` for a float64 [2, y, x] map that lives on the device (a
+  contiguous torch tensor or DeviceArray), without narrowing: the neighbour
+  differences are taken in double, as the reference does for a float64 map
+  (map_utils.py:769-775).  The map is masked in place.  Nothing comes to the
+  host: returns (mask [y, x] uint8, n_valid), both device tensors; n_valid is
+  the number of nodes that keep a component that is not NaN, so
+  `n_valid == 0` is the reference's `np.all(np.isnan(coord_map))`.
+  """
+  m = coord_map.tensor if isinstance(coord_map, DeviceArray) else coord_map
+  if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float64 and
+          m.is_contiguous() and m.ndim == 3 and m.shape[0] == 2):
+    raise ValueError('mask_irregular_f64 needs a contiguous float64 [2, y, x] device tensor')
+  if max_frac is None:
+    max_frac = 2 - frac
+  stride_x, stride_y = (float(v) for v in np.asarray(stride).ravel())
+  d = _irregular_desc(m.shape, stride_x, stride_y, frac, max_frac, dilation_iters)
+  bad = torch.empty(tuple(m.shape[1:]), dtype=torch.uint8, device=m.device)
+  n_valid = torch.empty((), dtype=torch.int32, device=m.device)
+  _abi.check(_abi.load().sfm_mask_irregular_f64(C.byref(d), m.data_ptr(), bad.data_ptr(),
+                                                n_valid.data_ptr()))
+  return bad, n_valid
 
 
 # reasons of a refused slice (SFM_INVMAP_* in include/sofima_amd.h)
