@@ -260,6 +260,66 @@ typedef struct SfmFlowScatterDesc {
 
 int sfm_flow_scatter(const SfmFlowScatterDesc* desc);
 
+/* Patch selection and ordered compaction of a 2-D flow_field() call in one
+ * launch (flow_field.py:570-589, :607, :614-618): a node of the [ny, nx] grid is
+ * selected where its selection byte is not 0 and, for each count plane given,
+ * !(double(count) / double(area) >= max_masked).  `positions` receives the
+ * (y, x) of the selected nodes in row-major order (np.where's); rows n ..
+ * total - 1 repeat row n - 1, total = ceil(n / batch_size) * batch_size;
+ * counts[0] = n, counts[1] = total (0 and 0 when nothing is selected).  The
+ * count planes are those of sfm_mask_patch_counts; their grids may be larger
+ * than [ny, nx] (the [out_sel] crop), never smaller (SFM_ERR_INVALID). */
+typedef struct SfmFlowSelectDesc {
+  int32_t grid[2];              /* ny, nx                                    */
+  int32_t batch_size;
+  int32_t capacity;             /* rows of `positions`, >= ceil(ny * nx / batch_size) * batch_size */
+  const uint8_t* selection;     /* device [ny, selection_pitch]              */
+  int32_t selection_pitch;      /* elements per row, >= nx                   */
+  int32_t pre_grid[2];          /* rows, columns of pre_counts               */
+  const int32_t* pre_counts;    /* device [pre_grid[0], pre_pitch] or NULL   */
+  int32_t pre_pitch;
+  int32_t pre_area;             /* pixels of a pre patch                     */
+  double pre_max_masked;
+  int32_t post_grid[2];
+  int32_t post_pitch;
+  int32_t post_area;
+  const int32_t* post_counts;   /* device [post_grid[0], post_pitch] or NULL */
+  double post_max_masked;
+  int32_t* positions;           /* out, device [capacity, 2]                 */
+  int32_t* counts;              /* out, device [2]: n, total                 */
+  void* stream;
+} SfmFlowSelectDesc;
+
+int sfm_flow_select(const SfmFlowSelectDesc* desc);
+
+/* The accept / update step of one look-back round of EstimateMissingFlow
+ * (processor/flow.py:806-828) and the attempts cap of the next round (:785).
+ * Per node of the [sy, sx] field (the top-left part of the [ny, nx] section):
+ * a finite field[0] counts an attempt; the node is updated where its mask byte
+ * is set, field[0] is finite and clean_flow(max_deviation = 0) would keep the
+ * vector; an update writes field[0], field[1] and delta_z into the three
+ * planes, clears the mask byte and is counted in *filled.  Then, for every
+ * node of the section, mask &= attempts <= max_attempts.  The thresholds are
+ * compared in double, as in SfmCleanFlowDesc; max_magnitude 0 disables that
+ * test.  *filled is added to, never cleared. */
+typedef struct SfmMissingFlowDesc {
+  int32_t shape[2];             /* ny, nx of the section                     */
+  int32_t field_shape[2];       /* sy <= ny, sx <= nx                        */
+  const float* field;           /* device [4, sy, sx]                        */
+  float* out[3];                /* device [ny, nx] planes: x, y, look-back   */
+  uint8_t* mask;                /* device [ny, nx], nodes still to estimate  */
+  int32_t* attempts;            /* device [ny, nx]                           */
+  double min_peak_ratio;
+  double min_peak_sharpness;
+  double max_magnitude;
+  int32_t delta_z;
+  int32_t max_attempts;
+  int64_t* filled;              /* device, this round's counter              */
+  void* stream;
+} SfmMissingFlowDesc;
+
+int sfm_missing_flow_update(const SfmMissingFlowDesc* desc);
+
 /* Stand-alone peak statistics, replaces _batched_peaks (flow_field.py:205-275)
  * for a caller-provided batch of surfaces.  A surface that holds a NaN or a
  * +inf has no peak (a NaN row; its first-peak index counts as 0 in the batch's

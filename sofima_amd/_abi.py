@@ -197,6 +197,47 @@ class SfmFlowScatterDesc(C.Structure):
   ]
 
 
+class SfmFlowSelectDesc(C.Structure):
+  _fields_ = [
+      ('grid', i32 * 2),
+      ('batch_size', i32),
+      ('capacity', i32),
+      ('selection', C.c_void_p),
+      ('selection_pitch', i32),
+      ('pre_grid', i32 * 2),
+      ('pre_counts', C.c_void_p),
+      ('pre_pitch', i32),
+      ('pre_area', i32),
+      ('pre_max_masked', C.c_double),
+      ('post_grid', i32 * 2),
+      ('post_pitch', i32),
+      ('post_area', i32),
+      ('post_counts', C.c_void_p),
+      ('post_max_masked', C.c_double),
+      ('positions', C.c_void_p),
+      ('counts', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
+class SfmMissingFlowDesc(C.Structure):
+  _fields_ = [
+      ('shape', i32 * 2),
+      ('field_shape', i32 * 2),
+      ('field', C.c_void_p),
+      ('out', C.c_void_p * 3),
+      ('mask', C.c_void_p),
+      ('attempts', C.c_void_p),
+      ('min_peak_ratio', C.c_double),
+      ('min_peak_sharpness', C.c_double),
+      ('max_magnitude', C.c_double),
+      ('delta_z', i32),
+      ('max_attempts', i32),
+      ('filled', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmWarpDesc(C.Structure):
   _fields_ = [
       ('dtype', i32),
@@ -496,6 +537,8 @@ SIGNATURES = {
     'sfm_prev_state': (C.c_int, [C.POINTER(SfmPrevStateDesc), C.c_void_p]),
     'sfm_flow_starts': (C.c_int, [C.POINTER(SfmFlowStartsDesc)]),
     'sfm_flow_scatter': (C.c_int, [C.POINTER(SfmFlowScatterDesc)]),
+    'sfm_flow_select': (C.c_int, [C.POINTER(SfmFlowSelectDesc)]),
+    'sfm_missing_flow_update': (C.c_int, [C.POINTER(SfmMissingFlowDesc)]),
     'sfm_warp_section': (C.c_int, [C.POINTER(SfmWarpDesc)]),
     'sfm_ndimage_warp': (C.c_int, [C.POINTER(SfmNdWarpDesc)]),
     'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),

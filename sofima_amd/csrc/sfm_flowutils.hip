@@ -8,6 +8,10 @@
 //   sfm_flow_starts     <->  the start-coordinate / targeting arithmetic of
 //                            flow_field() (flow_field.py:620-680)
 //   sfm_flow_scatter    <->  the result scatter of flow_field() (:701-709)
+//   sfm_flow_select     <->  patch selection and np.where of flow_field()
+//                            (:570-589, :607, :614-618), one launch
+//   sfm_missing_flow_update <-> the accept / update step of a look-back round
+//                            of EstimateMissingFlow (processor/flow.py:785, :806-828)
 //
 // One thread per vector.  The field is small (one vector per patch), so the
 // point of the kernel is that the flow can stay in HBM from the correlation
@@ -455,6 +459,217 @@ extern "C" int sfm_flow_scatter(const SfmFlowScatterDesc* d) {
   for (int i = 0; i < d->ndim; ++i) a.grid[i] = d->grid[3 - d->ndim + i];
   hipLaunchKernelGGL(flow_scatter_kernel, dim3((d->n + kBlock - 1) / kBlock), dim3(kBlock),
                      0, static_cast<hipStream_t>(d->stream), a);
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The look-back rounds of EstimateMissingFlow (processor/flow.py:739-838):
+// every round selects the nodes that are still missing, correlates them and
+// accepts what passes the thresholds.  The two kernels below are the planning
+// and the accept / update step of a round; the correlation lies between them.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kSelectBlock = 1024;
+constexpr int kSelectWaves = kSelectBlock / 64;
+
+struct SelectArgs {
+  const unsigned char* sel;
+  const int* counts[2];   // pre, post masked-pixel counts or NULL
+  int pitch[2], area[2];
+  double max_masked[2];
+  int* pos;               // [capacity, 2]
+  int* n_out;             // n, total
+  int ny, nx, sel_pitch, batch;
+};
+
+// ONE workgroup walks the grid in chunks of 1024 linear indices, so the order
+// of `pos` is the row-major order of np.where with nothing to wait for: the
+// rank inside a wave comes from a ballot, the 16 wave totals are summed through
+// LDS, the base is carried from chunk to chunk in a register.
+__global__ void __launch_bounds__(kSelectBlock) flow_select_kernel(SelectArgs a) {
+  __shared__ int wave_total[2][kSelectWaves];
+  __shared__ int last[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nodes = a.ny * a.nx;
+  int base = 0;
+  for (int start = 0, it = 0; start < nodes; start += kSelectBlock, ++it) {
+    const int i = start + tid;
+    bool keep = false;
+    int y = 0, x = 0;
+    if (i < nodes) {
+      y = i / a.nx;
+      x = i - y * a.nx;
+      keep = a.sel[(long long)y * a.sel_pitch + x] != 0;
+      for (int s = 0; s < 2; ++s)
+        if (keep && a.counts[s]) {
+          const int c = a.counts[s][(long long)y * a.pitch[s] + x];
+          // s / np.prod(patch) >= max_masked, in float64 (flow_field.py:579)
+          keep = !(static_cast<double>(c) / static_cast<double>(a.area[s]) >= a.max_masked[s]);
+        }
+    }
+    const unsigned long long votes = __ballot(keep);
+    const int rank = __popcll(votes & ((1ull << lane) - 1ull));
+    int* totals = wave_total[it & 1];   // two buffers: one barrier per chunk
+    if (lane == 0) totals[wave] = __popcll(votes);
+    __syncthreads();
+    int before = 0, chunk = 0;
+    for (int w = 0; w < kSelectWaves; ++w) {
+      const int t = totals[w];
+      before += w < wave ? t : 0;
+      chunk += t;
+    }
+    if (keep) {
+      const int row = base + before + rank;
+      a.pos[2 * row] = y;
+      a.pos[2 * row + 1] = x;
+      if (before + rank == chunk - 1) {   // the last one so far: the padding row
+        last[0] = y;
+        last[1] = x;
+      }
+    }
+    base += chunk;
+  }
+  __syncthreads();
+  const int n = base;
+  const int total = (n + a.batch - 1) / a.batch * a.batch;
+  // every batch is padded by repeating the LAST position (flow_field.py:614-618)
+  if (n > 0) {
+    const int ly = last[0], lx = last[1];
+    for (int row = n + tid; row < total; row += kSelectBlock) {
+      a.pos[2 * row] = ly;
+      a.pos[2 * row + 1] = lx;
+    }
+  }
+  if (tid == 0) {
+    a.n_out[0] = n;
+    a.n_out[1] = total;
+  }
+}
+
+struct MissingArgs {
+  const float* field;     // [4, sy, sx]
+  float* out[3];          // [ny, nx] each
+  unsigned char* mask;
+  int* attempts;
+  unsigned long long* filled;
+  double min_ratio, min_sharp, max_mag;
+  int ny, nx, sy, sx, delta_z, max_attempts;
+};
+
+__global__ void __launch_bounds__(kBlock) missing_flow_update_kernel(MissingArgs a) {
+  const int n = a.ny * a.nx;
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  bool update = false;
+  if (i < n) {
+    const int y = i / a.nx, x = i - y * a.nx;
+    bool m = a.mask[i] != 0;
+    int att = a.attempts[i];
+    if (y < a.sy && x < a.sx) {
+      const int fn = a.sy * a.sx, j = y * a.sx + x;
+      const float f0 = a.field[j], f1 = a.field[fn + j];
+      const float sharp = fabsf(a.field[2 * fn + j]), ratio = fabsf(a.field[3 * fn + j]);
+      const bool valid = isfinite(f0);
+      if (valid) att += 1;                 // counted whether or not the node is in the mask
+      // clean_flow with max_deviation = 0; comparisons with NaN are false, as in NumPy
+      bool bad = static_cast<double>(sharp) < a.min_sharp;
+      bad = bad || (ratio > 0.f && static_cast<double>(ratio) < a.min_ratio);
+      // np.max over the components propagates NaN, and NaN > t is false
+      if (a.max_mag > 0.0 && !isnan(f0) && !isnan(f1))
+        bad = bad || static_cast<double>(fmaxf(fabsf(f0), fabsf(f1))) > a.max_mag;
+      update = m && valid && !bad;
+      if (update) {
+        a.out[0][i] = f0;
+        a.out[1][i] = f1;
+        a.out[2][i] = static_cast<float>(a.delta_z);
+        m = false;
+      }
+    }
+    // the cap the next round applies before it selects (processor/flow.py:785)
+    m = m && att <= a.max_attempts;
+    a.mask[i] = m ? 1 : 0;
+    a.attempts[i] = att;
+  }
+  const int cnt = __popcll(__ballot(update));
+  if ((threadIdx.x & 63) == 0 && cnt)
+    atomicAdd(a.filled, static_cast<unsigned long long>(cnt));
+}
+
+}  // namespace
+
+extern "C" int sfm_flow_select(const SfmFlowSelectDesc* d) {
+  if (!d || !d->selection || !d->positions || !d->counts)
+    return sfm::fail(SFM_ERR_INVALID, "flow_select: NULL argument");
+  const long long ny = d->grid[0], nx = d->grid[1];
+  if (ny < 1 || nx < 1 || ny * nx > 0x7fffffffLL - kSelectBlock)
+    return sfm::fail(SFM_ERR_INVALID, "flow_select: bad grid");
+  if (d->batch_size < 1) return sfm::fail(SFM_ERR_INVALID, "flow_select: batch size");
+  if (d->selection_pitch < nx) return sfm::fail(SFM_ERR_INVALID, "flow_select: selection pitch");
+  const long long padded = (ny * nx + d->batch_size - 1) / d->batch_size * d->batch_size;
+  if (padded > 0x3fffffffLL || d->capacity < padded)
+    return sfm::fail(SFM_ERR_INVALID, "flow_select: capacity %d below %lld rows",
+                     d->capacity, padded);
+  SelectArgs a;
+  a.sel = d->selection;
+  a.sel_pitch = d->selection_pitch;
+  const int32_t* counts[2] = {d->pre_counts, d->post_counts};
+  const int32_t* cgrid[2] = {d->pre_grid, d->post_grid};
+  const int32_t cpitch[2] = {d->pre_pitch, d->post_pitch};
+  const int32_t carea[2] = {d->pre_area, d->post_area};
+  const double cmax[2] = {d->pre_max_masked, d->post_max_masked};
+  for (int s = 0; s < 2; ++s) {
+    a.counts[s] = counts[s];
+    a.pitch[s] = cpitch[s];
+    a.area[s] = carea[s];
+    a.max_masked[s] = cmax[s];
+    if (!counts[s]) continue;
+    if (cgrid[s][0] < ny || cgrid[s][1] < nx)
+      return sfm::fail(SFM_ERR_INVALID, "flow_select: count plane [%d, %d] smaller than the grid",
+                       cgrid[s][0], cgrid[s][1]);
+    if (cpitch[s] < cgrid[s][1] || carea[s] < 1)
+      return sfm::fail(SFM_ERR_INVALID, "flow_select: count pitch / patch area");
+  }
+  a.pos = d->positions;
+  a.n_out = d->counts;
+  a.ny = static_cast<int>(ny);
+  a.nx = static_cast<int>(nx);
+  a.batch = d->batch_size;
+  hipLaunchKernelGGL(flow_select_kernel, dim3(1), dim3(kSelectBlock), 0,
+                     static_cast<hipStream_t>(d->stream), a);
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
+}
+
+extern "C" int sfm_missing_flow_update(const SfmMissingFlowDesc* d) {
+  if (!d || !d->field || !d->out[0] || !d->out[1] || !d->out[2] || !d->mask || !d->attempts ||
+      !d->filled)
+    return sfm::fail(SFM_ERR_INVALID, "missing_flow_update: NULL argument");
+  const long long ny = d->shape[0], nx = d->shape[1];
+  if (ny < 1 || nx < 1 || ny * nx > 0x7fffffffLL - kBlock)
+    return sfm::fail(SFM_ERR_INVALID, "missing_flow_update: bad shape");
+  if (d->field_shape[0] < 1 || d->field_shape[1] < 1 || d->field_shape[0] > ny ||
+      d->field_shape[1] > nx)
+    return sfm::fail(SFM_ERR_INVALID, "missing_flow_update: field [%d, %d] outside the section",
+                     d->field_shape[0], d->field_shape[1]);
+  MissingArgs a;
+  a.field = d->field;
+  for (int c = 0; c < 3; ++c) a.out[c] = d->out[c];
+  a.mask = d->mask;
+  a.attempts = d->attempts;
+  a.filled = reinterpret_cast<unsigned long long*>(d->filled);
+  a.min_ratio = d->min_peak_ratio;
+  a.min_sharp = d->min_peak_sharpness;
+  a.max_mag = d->max_magnitude;
+  a.ny = static_cast<int>(ny);
+  a.nx = static_cast<int>(nx);
+  a.sy = d->field_shape[0];
+  a.sx = d->field_shape[1];
+  a.delta_z = d->delta_z;
+  a.max_attempts = d->max_attempts;
+  const unsigned grid = static_cast<unsigned>((ny * nx + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(missing_flow_update_kernel, dim3(grid), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(d->stream), a);
   SFM_LAUNCH_CHECK();
   return SFM_OK;
 }

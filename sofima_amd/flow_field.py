@@ -136,6 +136,18 @@ class _Resident:
     self.post_mask = _dev.as_device_mask(post_mask, dev)
     self.ndim = self.pre.ndim
 
+  @classmethod
+  def of_device(cls, pre, post, pre_mask, post_mask, dtype, dev):
+    """From tensors that are already what __init__ would make of them:
+    contiguous device images of one dtype (tag `dtype`), uint8 masks or None.
+    Nothing is converted or copied."""
+    res = cls.__new__(cls)
+    res.dev = dev
+    res.pre, res.post, res.dtype = pre, post, dtype
+    res.pre_mask, res.post_mask = pre_mask, post_mask
+    res.ndim = pre.ndim
+    return res
+
 
 def _make_desc(res: _Resident, patch_size, post_patch_size, mean, min_distance,
                threshold_rel, peak_radius, method) -> _abi.SfmXcorrDesc:
@@ -593,9 +605,23 @@ class JAXMaskedXCorrWithStatsCalculator:
           plan = self._plans.setdefault(key, plan)
           while len(self._plans) > 8:
             self._plans.popitem(last=False)   # its device tensors go with it
+    out = self.field_from_plan(res, plan, patch_size, post_patch_size, batch_size,
+                               mask_only_for_patch_selection, progress_fn)
+    if device_output:
+      return _dev.DeviceArray(out)
+    return out.cpu().numpy()
+
+  def field_from_plan(self, res: _Resident, plan: dict, patch_size, post_patch_size,
+                      batch_size, mask_only_for_patch_selection=False,
+                      progress_fn=_silent_fn) -> torch.Tensor:
+    """What flow_field() does once the patches are planned: correlates the
+    batches of a `device_plan()` and scatters the peaks into the NaN-filled
+    [dim + 2, *grid] field, a device tensor.  `plan` needs out_shape, n,
+    positions, starts, tg and po."""
+    nd = res.ndim
     out_shape = plan['out_shape']
     out = torch.full([nd + 2] + list(out_shape), float('nan'), dtype=torch.float32,
-                     device=dev)
+                     device=res.dev)
     n = plan['n']
     if n > 0:
       if mask_only_for_patch_selection:
@@ -623,9 +649,7 @@ class JAXMaskedXCorrWithStatsCalculator:
       sd.out = out.data_ptr()
       sd.stream = _dev.stream_ptr()
       _abi.check(_abi.load().sfm_flow_scatter(C.byref(sd)))
-    if device_output:
-      return _dev.DeviceArray(out)
-    return out.cpu().numpy()
+    return out
 
   def device_plan(self, res: _Resident, patch_size, step, selection_mask=None,
                   max_masked=0.75, batch_size=4096, post_patch_size=None,

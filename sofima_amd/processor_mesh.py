@@ -393,8 +393,9 @@ def relax_sections(flows: Sequence[FlowVolume],
   UNDEFINED / 0 / [].
 
   Not covered, and not parameters: `coming_in` regions, `ranges_to_skip` with
-  their custom flow volumes, an initial `mesh` volume, volume I/O, and
-  `EstimateMissingFlow` itself.
+  their custom flow volumes, an initial `mesh` volume and volume I/O.
+  `EstimateMissingFlow` itself, which produces the 3-channel flows, is
+  `processor_flow.estimate_missing_flow`.
   """
   if not flows:
     raise ValueError('no flows')
