@@ -4,6 +4,7 @@ from __future__ import annotations
 import os
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, 'csrc')
@@ -11,18 +12,28 @@ LIB_DIR = os.path.join(PKG_DIR, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libsofima_amd.so')
 OBJ_DIR = os.path.join(PKG_DIR, 'build')
 
-# Translation units and their extra flags.  The mesh kernels follow the
-# reference's f32 operation order, so FMA contraction is disabled there.
+# SFM_MFMA_TIMING / SFM_MFMA_FLAGS: instrumentation and tuning experiments, for the
+# units of the matrix-core correlation path
+_MFMA = ((['-DSFM_MFMA_TIMING'] if os.environ.get('SFM_MFMA_TIMING') else []) +
+         os.environ.get('SFM_MFMA_FLAGS', '').split())
+
+# The units of the matrix-core correlation path (csrc/sfm_mfma.h lists them; one unit
+# per chunk geometry of the correlation kernel): they all take the _MFMA flags
+MFMA_UNITS = ('sfm_mfma_g10x11.hip', 'sfm_mfma_g20x11.hip', 'sfm_mfma_g15x11.hip',
+              'sfm_mfma_g8x9.hip', 'sfm_mfma_g7x8.hip', 'sfm_mfma_g6x7.hip',
+              'sfm_mfma_g5x6.hip', 'sfm_mfma_g4x5.hip', 'sfm_mfma_g3x4.hip',
+              'sfm_xcorr_mfma.hip', 'sfm_mfma_host.hip')
+
+# Translation units and their extra flags, the slowest to compile first.  The mesh
+# kernels follow the reference's f32 operation order, so FMA contraction is disabled
+# there.
 SOURCES = {
-    'sfm_core.hip': [],
+    **{unit: _MFMA for unit in MFMA_UNITS},
     'sfm_mesh.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MESH_FLAGS', '').split(),
+    'sfm_core.hip': [],
     'sfm_xcorr.hip': [],
     'sfm_xcorr_fft.hip': [],
     'sfm_fft_own.hip': [],
-    # SFM_MFMA_TIMING / SFM_MFMA_FLAGS: instrumentation and tuning experiments
-    'sfm_xcorr_mfma.hip': ((['-DSFM_MFMA_TIMING']
-                            if os.environ.get('SFM_MFMA_TIMING') else []) +
-                           os.environ.get('SFM_MFMA_FLAGS', '').split()),
     'sfm_maps.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MAPS_FLAGS', '').split(),
     'sfm_flowutils.hip': ['-ffp-contract=off'],
     'sfm_invmap.hip': ['-ffp-contract=off'],
@@ -66,8 +77,29 @@ def _record(target: str, cmd: list[str]) -> None:
     f.write(' '.join(cmd))
 
 
+def jobs() -> int:
+  """Compiler processes at a time: MAX_JOBS if set, else the CPU count; 1 .. 16."""
+  try:
+    n = int(os.environ.get('MAX_JOBS', ''))
+  except ValueError:
+    n = os.cpu_count() or 1
+  return max(1, min(n, 16))
+
+
+def _compile(cmd: list[str], obj: str) -> subprocess.CompletedProcess:
+  # (a unit that fails must not leave an object that looks fresh)
+  for path in (obj, obj + '.cmd'):
+    if os.path.exists(path):
+      os.remove(path)
+  done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+  if done.returncode == 0:
+    _record(obj, cmd)
+  return done
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
-  """Compiles every HIP translation unit for gfx950 and links the library."""
+  """Compiles every HIP translation unit for gfx950, the stale ones side by side,
+  and links the library."""
   os.makedirs(LIB_DIR, exist_ok=True)
   os.makedirs(OBJ_DIR, exist_ok=True)
   headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC)
@@ -75,7 +107,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
   headers.append(os.path.join(PKG_DIR, '..', 'include', 'sofima_amd.h'))
   hipcc = _hipcc()
   objs = []
-  relink = force
+  stale = []
   for src, extra in SOURCES.items():
     src_path = os.path.join(CSRC, src)
     obj = os.path.join(OBJ_DIR, src + '.o')
@@ -84,10 +116,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if force or _stale(obj, [src_path] + headers, cmd):
       if verbose:
         print(' '.join(cmd))
-      subprocess.run(cmd, check=True)
-      _record(obj, cmd)
-      relink = True
-  if relink or _stale(LIB_PATH, objs):
+      stale.append((src, cmd, obj))
+  with ThreadPoolExecutor(max_workers=jobs()) as pool:
+    results = list(pool.map(lambda job: _compile(job[1], job[2]), stale))
+  for (src, _, _), done in zip(stale, results):
+    if done.returncode != 0:
+      # (the library, if any, is older than the source that failed: still stale)
+      raise RuntimeError('%s failed to compile:\n%s' % (src, done.stdout))
+    if done.stdout:   # warnings
+      print(done.stdout, end='')
+  if stale or _stale(LIB_PATH, objs):
     # no library dependency beyond the HIP runtime (RCCL is resolved with dlsym)
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB_PATH
            ] + objs + ['-L/opt/rocm/lib', '-ldl', '-Wl,-rpath,/opt/rocm/lib']

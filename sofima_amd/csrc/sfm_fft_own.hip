@@ -24,7 +24,7 @@
 // pencils of a tile (strided passes) or along the pencil (x passes).  A y axis
 // beyond one tile (whole-overlap strips: 8192) takes two strided passes with a
 // twiddle in between (four-step split; see PencilArgs).
-#include "sfm_common.h"
+#include "sfm_xcorr_units.h"
 
 #include <cmath>
 #include <cstdlib>

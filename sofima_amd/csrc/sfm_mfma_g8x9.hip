@@ -1,0 +1,4 @@
+// xcorr_mfma_kernel<8, 9, *>: one chunk geometry of the correlation kernel.
+#include "sfm_mfma_kernel.h"
+
+SFM_MFMA_GEOMETRY_UNIT(8, 9)

@@ -17,35 +17,11 @@
 // which is the same quantity (oracle/flow_oracle.py checks both forms against
 // the reference's own output).  The masked (Padfield) surface is assembled
 // from six such sums exactly as SURVEY.md section 8a derives.
-#include "sfm_common.h"
+#include "sfm_xcorr_units.h"
 
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-
-namespace sfm {
-// Implemented in sfm_xcorr_mfma.hip.
-bool mfma_i8_eligible(const SfmXcorrDesc* d);
-size_t mfma_i8_workspace_bytes(const SfmXcorrDesc* d);
-// Writes a surface padded to whole 16 x 16 tiles: [B, rows, pitch].
-int mfma_i8_surface(const SfmXcorrDesc* d, void* ws, float* surface,
-                    const FusedPeaks* fused);
-void mfma_i8_padded_dims(const SfmXcorrDesc* d, int* rows, int* pitch);
-// sfm_xcorr_fft.hip
-bool fft_preferred(const SfmXcorrDesc* d);
-int fft_check(const SfmXcorrDesc* d);
-size_t fft_workspace_bytes(const SfmXcorrDesc* d);
-int fft_correlate(const SfmXcorrDesc* d, const float* a0, const float* b0,
-                  const float* va, const float* vb, float* surface, float* den,
-                  float* ov, unsigned int* maxima, void* ws, unsigned int* smax);
-// Masked correlation: the normalised surface, padded to whole tiles; `smax`
-// (optional, zeroed by the caller) receives the ordered bits of every surface
-// maximum for the peak search.
-int mfma_i8_masked(const SfmXcorrDesc* d, void* ws, float* surface,
-                   unsigned int* maxima, unsigned int* smax, float* blkmax);
-// rows per block of `blkmax` (the assembly workgroups take 4 waves x 8 rows)
-constexpr int kMaskedBlkRows = 32;
-}  // namespace sfm
 
 namespace {
 

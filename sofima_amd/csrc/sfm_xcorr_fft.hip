@@ -11,7 +11,7 @@
 //
 //   corr[k] = sum_i a[i + k - (Q - 1)] b[i]
 //           = irfft(rfft(a_pad) conj(rfft(b_pad)))[(k - (Q - 1)) mod F]
-#include "sfm_common.h"
+#include "sfm_xcorr_units.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -21,26 +21,6 @@
 #include <tuple>
 
 namespace sfm {
-
-// sfm_fft_own.hip: the hand-written transforms
-bool own_fft_supported(int rank, const int* F);
-bool own_fft_fits_tile(int n);
-// in-plane patches beyond one tile along both axes (full-complex path)
-bool own_fft_big_supported(int rank, const int* F);
-int own_fft_big_correlate(const int* P, const int* Q, const int* S, const int* F, int nb,
-                          const float* a0, const float* b0, float2* sa, float2* sb, float2* tmp,
-                          float* surface, unsigned int* smax, hipStream_t st);
-int own_fft_big_forward(const int* R, const int* F, int nb, const float* src, int square,
-                        float2* spec, float2* tmp, hipStream_t st);
-int own_fft_big_inverse_product(const int* F, int nb, const float2* lhs, const float2* rhs,
-                                float2* work, float2* tmp, float* real_out, hipStream_t st);
-int own_fft_correlate(const int* P, const int* Q, const int* S, const int* F, int nb,
-                      const float* a0, const float* b0, float2* sa, float2* sb, float* surface,
-                      unsigned int* smax, hipStream_t st);
-int own_fft_forward(const int* R, const int* F, int nb, const float* src, int square,
-                    float2* spec, hipStream_t st);
-int own_fft_inverse_product(const int* F, int nb, const float2* lhs, const float2* rhs,
-                            float2* work, float* real_out, hipStream_t st);
 
 namespace {
 

@@ -37,7 +37,7 @@ from . import _abi
 from . import _dev
 
 T = TypeVar("T")
-# The uint8 2-D unmasked path runs on the int8 matrix cores (sfm_xcorr_mfma.hip).
+# The uint8 2-D unmasked path runs on the int8 matrix cores (csrc/sfm_mfma.h).
 MFMA_I8_AVAILABLE = True
 Array = np.ndarray
 

@@ -112,7 +112,7 @@ def test_correction_bound_of_the_seed_probe():
 # ---------------------------------------------------------------------------
 # Round-4 inequalities ("cold tiles abandoned inside their row
 # loop", "row loops that narrow themselves", "the guard band is counted in
-# rows"): NumPy restatements of what sfm_xcorr_mfma.hip's check_after and the
+# rows"): NumPy restatements of what sfm_mfma_kernel.h's check_after and the
 # end-of-patch need mask rely on, against directly computed partial surfaces.
 # ---------------------------------------------------------------------------
 def _int_centre(x):
