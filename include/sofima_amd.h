@@ -436,6 +436,48 @@ size_t sfm_reconcile_flows_workspace_bytes(const SfmReconcileDesc* desc);
 int sfm_reconcile_flows(const SfmReconcileDesc* desc, float* out);
 
 /* ------------------------------------------------------------------------
+ * The fine flows of a tile montage: clean_flow, then reconcile_flows of that
+ * one flow, for a ragged batch of n in-plane tile-pair flows in ONE launch
+ * (one workgroup per pair, the pair stays in LDS).  Pair p occupies
+ * flows[:, p, :h, :w] of the packed [channels, n, Y, X] input, (h, w) =
+ * extents[p]; what lies outside is never read.  Every pair is filtered on its
+ * own extent -- borders, the 3 x 3 "reflect" windows and the invalid count of
+ * the small-component test are those of [h, w], not of [Y, X] -- and gives,
+ * bit for bit, what sfm_clean_flow (z = 1, dim = 2) followed by
+ * sfm_reconcile_flows (K = 1, 2 channels) give for that pair alone, with the
+ * comparison rules of SfmCleanFlowDesc / SfmReconcileDesc.  4 channels:
+ * channel 2 is the peak sharpness, channel 3 the peak ratio.  do_clean = 0
+ * takes channels 0 / 1 as they are; do_reconcile = 0 stops after the clean-up.
+ * A pair holds at most sfm_filter_tile_flows_max_nodes() vectors (what 160 KB
+ * of LDS hold at 12 bytes per vector).
+ * ---------------------------------------------------------------------- */
+typedef struct SfmTileFlowsDesc {
+  int32_t channels;             /* 2 or 4                                    */
+  int32_t n;                    /* tile pairs                                */
+  int32_t padded_shape[2];      /* Y, X of the packed arrays                 */
+  const int32_t* extents;       /* HOST [n, 2]: h, w of every pair           */
+  const int32_t* extents_device;/* the same table in device memory           */
+  double min_peak_ratio;        /* clean-up, 4 channels only                 */
+  double min_peak_sharpness;
+  double max_magnitude;         /* <= 0: not applied                         */
+  double clean_max_deviation;   /* <= 0: not applied                         */
+  double max_gradient;          /* reconciliation; <= 0: not applied         */
+  double max_deviation;         /* <= 0: not applied                         */
+  double min_delta_z;           /* 3-channel flows only: not read            */
+  int64_t min_patch_size;       /* <= 0: not applied                         */
+  int32_t do_clean;
+  int32_t do_reconcile;
+  const float* flows;           /* device [channels, n, Y, X]                */
+  void* stream;
+} SfmTileFlowsDesc;
+
+/* out: device float [2, n, Y, X], NaN outside a pair's extent; must not
+ * overlap flows. */
+int sfm_filter_tile_flows(const SfmTileFlowsDesc* desc, float* out);
+/* Host arithmetic only (callable without a GPU). */
+int sfm_filter_tile_flows_max_nodes(void);
+
+/* ------------------------------------------------------------------------
  * Inversion of an in-plane coordinate map, the step between mesh relaxation
  * and warping.  Replaces the 2-D branch of map_utils.invert_map
  * (map_utils.py:392-463): per z slice, the valid nodes (both channels finite)

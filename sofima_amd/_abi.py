@@ -134,6 +134,28 @@ class SfmReconcileDesc(C.Structure):
   ]
 
 
+class SfmTileFlowsDesc(C.Structure):
+  _fields_ = [
+      ('channels', i32),
+      ('n', i32),
+      ('padded_shape', i32 * 2),
+      ('extents', C.c_void_p),
+      ('extents_device', C.c_void_p),
+      ('min_peak_ratio', C.c_double),
+      ('min_peak_sharpness', C.c_double),
+      ('max_magnitude', C.c_double),
+      ('clean_max_deviation', C.c_double),
+      ('max_gradient', C.c_double),
+      ('max_deviation', C.c_double),
+      ('min_delta_z', C.c_double),
+      ('min_patch_size', C.c_int64),
+      ('do_clean', i32),
+      ('do_reconcile', i32),
+      ('flows', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmInvertMapDesc(C.Structure):
   _fields_ = [
       ('shape', i32 * 3),
@@ -528,6 +550,8 @@ SIGNATURES = {
     'sfm_clean_flow': (C.c_int, [C.POINTER(SfmCleanFlowDesc), C.c_void_p]),
     'sfm_reconcile_flows_workspace_bytes': (C.c_size_t, [C.POINTER(SfmReconcileDesc)]),
     'sfm_reconcile_flows': (C.c_int, [C.POINTER(SfmReconcileDesc), C.c_void_p]),
+    'sfm_filter_tile_flows': (C.c_int, [C.POINTER(SfmTileFlowsDesc), C.c_void_p]),
+    'sfm_filter_tile_flows_max_nodes': (C.c_int, []),
     'sfm_invert_map_workspace_bytes': (C.c_size_t, [C.POINTER(SfmInvertMapDesc)]),
     'sfm_invert_map': (C.c_int, [C.POINTER(SfmInvertMapDesc), C.c_void_p]),
     'sfm_mask_irregular': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,

@@ -36,6 +36,7 @@ SOURCES = {
     'sfm_fft_own.hip': [],
     'sfm_maps.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MAPS_FLAGS', '').split(),
     'sfm_flowutils.hip': ['-ffp-contract=off'],
+    'sfm_tileflows.hip': ['-ffp-contract=off'],
     'sfm_invmap.hip': ['-ffp-contract=off'],
     'sfm_comm.hip': [],
     'sfm_warp.hip': ['-ffp-contract=off'],

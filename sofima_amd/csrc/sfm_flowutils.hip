@@ -17,10 +17,14 @@
 // point of the kernel is that the flow can stay in HBM from the correlation
 // peaks to the mesh relaxation; it is bound by launch latency.
 #include "sfm_common.h"
+#include "sfm_flowfilter.h"
 
 #include <hip/hip_runtime.h>
 
 namespace {
+
+// window, border and comparison rules shared with sfm_tileflows.hip
+using namespace sfm::flowfilter;
 
 constexpr int kBlock = 256;
 
@@ -31,21 +35,6 @@ struct CleanArgs {
   int Z, Y, X;
   double min_ratio, min_sharp, max_mag, max_dev;  // compared in double, see SfmCleanFlowDesc
 };
-
-// np.nan_to_num for float32: NaN -> 0, +-inf -> +-FLT_MAX.
-__device__ __forceinline__ float nan_to_num(float v) {
-  if (isnan(v)) return 0.f;
-  if (isinf(v)) return v > 0.f ? 3.4028234663852886e38f : -3.4028234663852886e38f;
-  return v;
-}
-
-// scipy.ndimage "reflect" boundary (d c b a | a b c d | d c b a) for a
-// one-element overhang.
-__device__ __forceinline__ int reflect(int i, int n) {
-  if (i < 0) return -i - 1 < n ? -i - 1 : n - 1;
-  if (i >= n) return 2 * n - 1 - i >= 0 ? 2 * n - 1 - i : 0;
-  return i;
-}
 
 // Median of the (1|3) x 3 x 3 window of nan_to_num(comp) around (z, y, x).
 __device__ float window_median(const float* comp, const CleanArgs& a, int z, int y,
@@ -58,13 +47,7 @@ __device__ float window_median(const float* comp, const CleanArgs& a, int z, int
       for (int dx = -1; dx <= 1; ++dx) {
         const int zz = reflect(z + dz, a.Z), yy = reflect(y + dy, a.Y),
                   xx = reflect(x + dx, a.X);
-        const float v = nan_to_num(comp[((long long)zz * a.Y + yy) * a.X + xx]);
-        int k = n++;  // insertion sort
-        while (k > 0 && w[k - 1] > v) {
-          w[k] = w[k - 1];
-          --k;
-        }
-        w[k] = v;
+        insert_sorted(w, n, nan_to_num(comp[((long long)zz * a.Y + yy) * a.X + xx]));
       }
   return w[n / 2];
 }
@@ -78,10 +61,8 @@ __global__ void __launch_bounds__(kBlock) clean_flow_kernel(CleanArgs a) {
   const int z = static_cast<int>(i / ((long long)a.X * a.Y));
   bool bad = false;
   if (a.channels == a.dim + 2) {
-    // comparisons with NaN are false, as in NumPy
-    bad = static_cast<double>(fabsf(a.flow[a.dim * n_vec + i])) < a.min_sharp;
-    const float pr = fabsf(a.flow[(a.dim + 1) * n_vec + i]);
-    bad = bad || (pr > 0.f && static_cast<double>(pr) < a.min_ratio);
+    bad = peak_bad(a.flow[a.dim * n_vec + i], a.flow[(a.dim + 1) * n_vec + i], a.min_sharp,
+                   a.min_ratio);
   }
   float v[3];
   bool any_nan = false;
@@ -94,7 +75,7 @@ __global__ void __launch_bounds__(kBlock) clean_flow_kernel(CleanArgs a) {
     if (a.max_mag > 0.0) {
       float m = 0.f;
       for (int c = 0; c < a.dim; ++c) m = fmaxf(m, fabsf(v[c]));
-      bad = bad || static_cast<double>(m) > a.max_mag;
+      bad = bad || above(m, a.max_mag);
     }
     if (a.max_dev > 0.0) {
       float m = 0.f;
@@ -102,7 +83,7 @@ __global__ void __launch_bounds__(kBlock) clean_flow_kernel(CleanArgs a) {
         const float med = window_median(a.flow + c * n_vec, a, z, y, x);
         m = fmaxf(m, fabsf(med - v[c]));
       }
-      bad = bad || static_cast<double>(m) > a.max_dev;
+      bad = bad || above(m, a.max_dev);
     }
   }
   for (int c = 0; c < a.dim; ++c) a.out[c * n_vec + i] = bad ? NAN : v[c];
@@ -761,40 +742,23 @@ __global__ void __launch_bounds__(kBlock) reconcile_merge_kernel(ReconcileArgs a
   for (int c = 0; c < a.C; ++c) v[c] = merged_at(a, n, i, c);
   bool bad = false;
   if (a.max_grad > 0.0) {
-    // np.diff with prepend=0 / append=0: the int64 zero promotes the field to
-    // float64, so the differences are taken in double; a missing neighbour is 0;
-    // |a-b| > t is false for a NaN difference
+    // a missing neighbour is 0 (gradient_bad)
     const int x = static_cast<int>(i % a.X);
     const int y = static_cast<int>((i / a.X) % a.Y);
     const float l = x > 0 ? merged_at(a, n, i - 1, 0) : 0.f;
     const float r = x + 1 < a.X ? merged_at(a, n, i + 1, 0) : 0.f;
     const float u = y > 0 ? merged_at(a, n, i - a.X, 1) : 0.f;
     const float d = y + 1 < a.Y ? merged_at(a, n, i + a.X, 1) : 0.f;
-    const double c0 = v[0], c1 = v[1];
-    bad = fabs(c0 - static_cast<double>(l)) > a.max_grad ||
-          fabs(static_cast<double>(r) - c0) > a.max_grad ||
-          fabs(c1 - static_cast<double>(u)) > a.max_grad ||
-          fabs(static_cast<double>(d) - c1) > a.max_grad;
+    bad = gradient_bad(v[0], v[1], l, r, u, d, a.max_grad);
   }
   for (int c = 0; c < a.C; ++c) a.dst[c * n + i] = bad ? NAN : v[c];
 }
 
 // Median of the 3 x 3 window of nan_to_num(comp) in one z slice (reflect).
 __device__ float median9(const float* comp, const ReconcileArgs& a, int z, int y, int x) {
-  float w[9];
-  int n = 0;
-  for (int dy = -1; dy <= 1; ++dy)
-    for (int dx = -1; dx <= 1; ++dx) {
-      const int yy = reflect(y + dy, a.Y), xx = reflect(x + dx, a.X);
-      const float v = nan_to_num(comp[((long long)z * a.Y + yy) * a.X + xx]);
-      int k = n++;  // insertion sort
-      while (k > 0 && w[k - 1] > v) {
-        w[k] = w[k - 1];
-        --k;
-      }
-      w[k] = v;
-    }
-  return w[4];
+  const float* plane = comp + (long long)z * a.Y * a.X;
+  return median3x3([&](int yy, int xx) { return plane[(long long)yy * a.X + xx]; }, y, x, a.Y,
+                   a.X);
 }
 
 __global__ void __launch_bounds__(kBlock) reconcile_median_kernel(ReconcileArgs a) {
@@ -804,51 +768,14 @@ __global__ void __launch_bounds__(kBlock) reconcile_median_kernel(ReconcileArgs 
   const int x = static_cast<int>(i % a.X);
   const int y = static_cast<int>((i / a.X) % a.Y);
   const int z = static_cast<int>(i / ((long long)a.X * a.Y));
-  // np.max over channels 0 and 1 propagates NaN, and NaN > t is false
   const float d0 = fabsf(median9(a.src, a, z, y, x) - a.src[i]);
   const float d1 = fabsf(median9(a.src + n, a, z, y, x) - a.src[n + i]);
-  const bool bad =
-      !isnan(d0) && !isnan(d1) && static_cast<double>(fmaxf(d0, d1)) > a.max_dev;
+  const bool bad = deviation_bad(d0, d1, a.max_dev);
   for (int c = 0; c < a.C; ++c) a.dst[c * n + i] = bad ? NAN : a.src[c * n + i];
 }
 
-__device__ __forceinline__ int load_parent(const int* p, int i) {
-  return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int lower_parent(int* p, int i, int v) {
-  return __hip_atomic_fetch_min(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Root of i, halving the path on the way (p[i] <- p[p[i]], never upwards).
-__device__ int find_root(int* p, int i) {
-  while (true) {
-    const int q = load_parent(p, i);
-    if (q == i) return i;
-    const int g = load_parent(p, q);
-    if (g == q) return q;
-    lower_parent(p, i, g);
-    i = g;
-  }
-}
-
-// Hooks the larger root under the smaller; when the hook loses a race (the
-// larger root got a parent meanwhile) it retries from that parent.
-__device__ void unite(int* p, int a, int b) {
-  while (true) {
-    a = find_root(p, a);
-    b = find_root(p, b);
-    if (a == b) return;
-    if (a > b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = lower_parent(p, b, a);
-    if (old == b) return;
-    b = old;
-  }
-}
+// the parent array lives in global memory, shared by all workgroups
+constexpr int kScope = __HIP_MEMORY_SCOPE_AGENT;
 
 __global__ void __launch_bounds__(kBlock) ccl_init_kernel(ReconcileArgs a) {
   const long long n = (long long)a.Z * a.Y * a.X;
@@ -865,12 +792,14 @@ __global__ void __launch_bounds__(kBlock) ccl_union_kernel(ReconcileArgs a) {
   const long long il = blockIdx.x * (long long)kBlock + threadIdx.x;
   if (il >= n) return;
   const int i = static_cast<int>(il);
-  if (load_parent(a.parent, i) < 0) return;
+  if (load_parent<kScope>(a.parent, i) < 0) return;
   const int x = i % a.X;
   const int y = (i / a.X) % a.Y;
   // right and down neighbours of the same slice: the cross structure
-  if (x + 1 < a.X && load_parent(a.parent, i + 1) >= 0) unite(a.parent, i, i + 1);
-  if (y + 1 < a.Y && load_parent(a.parent, i + a.X) >= 0) unite(a.parent, i, i + a.X);
+  if (x + 1 < a.X && load_parent<kScope>(a.parent, i + 1) >= 0)
+    unite<kScope>(a.parent, i, i + 1);
+  if (y + 1 < a.Y && load_parent<kScope>(a.parent, i + a.X) >= 0)
+    unite<kScope>(a.parent, i, i + a.X);
 }
 
 // parent[i] <- root; component sizes at the roots; invalid vectors per slice.

@@ -42,12 +42,9 @@ def clean_flow(flow, min_peak_ratio: float, min_peak_sharpness: float,
   d.dim = dim
   d.channels = f.shape[0]
   d.shape = (C.c_int32 * 3)(*f.shape[1:])
-  d.min_peak_ratio = _f32_threshold(min_peak_ratio)
-  d.min_peak_sharpness = _f32_threshold(min_peak_sharpness)
-  # a positive threshold that float32 rounds to 0 still enables the test: for a
-  # float32 x, `x > 0` is `x > 5e-324` in double
-  d.max_magnitude = max(_f32_threshold(max_magnitude), 5e-324) if max_magnitude > 0 else 0.0
-  d.max_deviation = max(_f32_threshold(max_deviation), 5e-324) if max_deviation > 0 else 0.0
+  (d.min_peak_ratio, d.min_peak_sharpness, d.max_magnitude,
+   d.max_deviation) = _clean_thresholds(min_peak_ratio, min_peak_sharpness, max_magnitude,
+                                        max_deviation)
   d.flow = f.data_ptr()
   d.stream = _dev.stream_ptr()
   out = torch.empty((dim,) + tuple(f.shape[1:]), dtype=torch.float32, device=dev)
@@ -62,6 +59,30 @@ def _f32_threshold(t) -> float:
   if np.result_type(np.float32, t) == np.float32:
     return float(np.float32(t))
   return float(t)
+
+
+def _positive_f32_threshold(t) -> float:
+  """`_f32_threshold` of a limit that is applied only when it is > 0.  A positive
+  threshold that float32 rounds to 0 still enables the test: for a float32 x,
+  `x > 0` is `x > 5e-324` in double."""
+  return max(_f32_threshold(t), 5e-324) if t > 0 else 0.0
+
+
+def _clean_thresholds(min_peak_ratio, min_peak_sharpness, max_magnitude, max_deviation):
+  """clean_flow's thresholds as the doubles SfmCleanFlowDesc carries."""
+  return (_f32_threshold(min_peak_ratio), _f32_threshold(min_peak_sharpness),
+          _positive_f32_threshold(max_magnitude), _positive_f32_threshold(max_deviation))
+
+
+def _reconcile_thresholds(max_gradient, max_deviation, min_patch_size, min_delta_z=0):
+  """reconcile_flows' thresholds as SfmReconcileDesc carries them."""
+  return (
+      # np.diff's zero padding makes the gradient float64 whatever the threshold
+      float(max_gradient) if max_gradient > 0 else 0.0,
+      _positive_f32_threshold(max_deviation),
+      # integer sizes: size < m <=> size < ceil(m)
+      max(0, min(int(math.ceil(min_patch_size)), 2**62)),
+      _f32_threshold(min_delta_z))
 
 
 def reconcile_flows(flows, max_gradient: float, max_deviation: float,
@@ -105,14 +126,9 @@ def reconcile_flows(flows, max_gradient: float, max_deviation: float,
   d.channels = shape[0]
   d.shape = (C.c_int32 * 3)(*shape[1:])
   d.num_flows = packed.shape[0]
-  # np.diff's zero padding makes the gradient float64 whatever the threshold
-  d.max_gradient = float(max_gradient) if max_gradient > 0 else 0.0
-  # a positive threshold that float32 rounds to 0 still enables the test: for a
-  # float32 x, `x > 0` is `x > 5e-324` in double
-  d.max_deviation = max(_f32_threshold(max_deviation), 5e-324) if max_deviation > 0 else 0.0
-  d.min_delta_z = _f32_threshold(min_delta_z)
-  # integer sizes: size < m <=> size < ceil(m)
-  d.min_patch_size = max(0, min(int(math.ceil(min_patch_size)), 2**62))
+  (d.max_gradient, d.max_deviation, d.min_patch_size,
+   d.min_delta_z) = _reconcile_thresholds(max_gradient, max_deviation, min_patch_size,
+                                          min_delta_z)
   d.flows = packed.data_ptr()
   lib = _abi.load()
   nbytes = lib.sfm_reconcile_flows_workspace_bytes(C.byref(d))
