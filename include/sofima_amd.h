@@ -41,7 +41,8 @@ extern "C" {
                                    sfm_affine_map and sfm_warp_points were added
                                    without a bump: new entry points only, no
                                    existing struct or call changed; likewise
-                                   sfm_prev_state and sfm_mask_irregular_f64 */
+                                   sfm_prev_state, sfm_mask_irregular_f64 and
+                                   sfm_render_tiles3d */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -661,6 +662,55 @@ typedef struct SfmNdWarpDesc {
 } SfmNdWarpDesc;
 
 int sfm_ndimage_warp(const SfmNdWarpDesc* desc);
+
+/* ------------------------------------------------------------------------
+ * processor/warp.py: StitchAndRender3dTiles.process (:292-343), the warp-and-
+ * blend loop of a 3-D tile montage, as ONE kernel per output box.  Every output
+ * voxel walks the request's tile table in ascending order; for a tile whose
+ * sub_box holds it the voxel computes, as warp.ndimage_warp does (see above),
+ * the node-space position and the three dense source coordinates ONCE, samples
+ * the image region data_box (order 0 / 1, converted to the tile dtype as SciPy
+ * does) and the tile's 2-D blend weights repeated along z (order 1, narrowed to
+ * float32), and accumulates img += float32(image) * w, norm += w in float32.
+ * Where norm > 0 the voxel is the IEEE float32 quotient img / norm, elsewhere
+ * img (0 where no tile reaches); the result is cast by truncation and stored
+ * once.  The absolute source map of a (tile, request) pair is read as
+ * abs_map + shift: abs_map is the tile's float64 inverse map plus node index x
+ * stride (sfm_map_shift, SFM_SHIFT_TO_ABSOLUTE, no box) and shift the scalar
+ * tg_box.start * stride - data_box.start per channel, the two sums of
+ * warp.py:249-258 in their order.
+ * ---------------------------------------------------------------------- */
+typedef struct SfmRenderTile {
+  const void* image;            /* device [z, y, x]: the WHOLE tile            */
+  const double* abs_map;        /* device [3, z, y, x] float64, channels x, y, z */
+  const float* weights;         /* device [y, x] float32 of the whole tile     */
+  int32_t tile_shape[3];        /* z, y, x of image (y, x of weights)          */
+  int32_t map_shape[3];         /* z, y, x nodes                               */
+  int32_t data_start[3];        /* z, y, x of data_box within the tile         */
+  int32_t data_size[3];         /* z, y, x of data_box                         */
+  int32_t sub_start[3];         /* z, y, x of sub_box within the output box    */
+  int32_t sub_size[3];          /* z, y, x of sub_box                          */
+  double shift[3];              /* per channel x, y, z: added to abs_map       */
+  double offset[3];             /* z, y, x of map node 0 relative to voxel 0 of
+                                   sub_box (warp.py:288)                       */
+} SfmRenderTile;
+
+typedef struct SfmRenderTilesDesc {
+  int32_t dtype;                /* SFM_DTYPE_U8 | U16 | F32 of the tiles       */
+  int32_t out_dtype;            /* dtype, or SFM_DTYPE_F32                     */
+  int32_t order;                /* image sampling: 0 nearest, 1 linear         */
+  int32_t n_tiles;              /* entries of the table, >= 0                  */
+  int32_t out_shape[3];         /* z, y, x of the output box                   */
+  double stride[3];             /* z, y, x output voxels per map node          */
+  const SfmRenderTile* tiles_host;  /* host copy of the table: every box is
+                                   checked against its array before the launch */
+  const SfmRenderTile* tiles;   /* device copy of the same table, read by the
+                                   kernel (NULL allowed when n_tiles is 0)     */
+  void* out;                    /* device [z, y, x] of out_dtype, all written  */
+  void* stream;
+} SfmRenderTilesDesc;
+
+int sfm_render_tiles3d(const SfmRenderTilesDesc* desc);
 
 /* ------------------------------------------------------------------------
  * Map geometry: the one-pass helpers that the reference's renderers call

@@ -296,6 +296,37 @@ class SfmNdWarpDesc(C.Structure):
   ]
 
 
+class SfmRenderTile(C.Structure):
+  _fields_ = [
+      ('image', C.c_void_p),
+      ('abs_map', C.c_void_p),
+      ('weights', C.c_void_p),
+      ('tile_shape', i32 * 3),
+      ('map_shape', i32 * 3),
+      ('data_start', i32 * 3),
+      ('data_size', i32 * 3),
+      ('sub_start', i32 * 3),
+      ('sub_size', i32 * 3),
+      ('shift', C.c_double * 3),
+      ('offset', C.c_double * 3),
+  ]
+
+
+class SfmRenderTilesDesc(C.Structure):
+  _fields_ = [
+      ('dtype', i32),
+      ('out_dtype', i32),
+      ('order', i32),
+      ('n_tiles', i32),
+      ('out_shape', i32 * 3),
+      ('stride', C.c_double * 3),
+      ('tiles_host', C.POINTER(SfmRenderTile)),
+      ('tiles', C.c_void_p),
+      ('out', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
 SHIFT_TO_ABSOLUTE = 0
 SHIFT_TO_RELATIVE = 1
 EXTENTS_OUTER = 0
@@ -565,6 +596,7 @@ SIGNATURES = {
     'sfm_missing_flow_update': (C.c_int, [C.POINTER(SfmMissingFlowDesc)]),
     'sfm_warp_section': (C.c_int, [C.POINTER(SfmWarpDesc)]),
     'sfm_ndimage_warp': (C.c_int, [C.POINTER(SfmNdWarpDesc)]),
+    'sfm_render_tiles3d': (C.c_int, [C.POINTER(SfmRenderTilesDesc)]),
     'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),
     'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
     'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),

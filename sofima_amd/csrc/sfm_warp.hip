@@ -12,6 +12,7 @@
 // host side builds them like OpenCV's initInterTab2D: 32 x 32 sub-pixel phases,
 // ksize x ksize taps; 15-bit fixed point for 8-bit images).
 #include "sfm_common.h"
+#include "sfm_ndsample.h"
 
 #include <cmath>
 
@@ -196,81 +197,6 @@ struct NdWarpArgs {
   double stride[3], offset[3];
 };
 
-// scipy NI_GeometricTransform, order 1, mode "constant", cval 0: outside
-// [0, len - 1] on any axis, NaN included -> 0; the tap beyond the last sample
-// (coordinate exactly len - 1) carries weight 0 and is read mirrored, from
-// len - 2, as SciPy's edge mapping does: 0 x inf and 0 x NaN there are NaN.
-template <int DIM, typename T>
-__device__ __forceinline__ double linear_sample(const T* __restrict__ a, const int* shape,
-                                                const double* c) {
-  long long base[DIM];
-  double w[DIM][2];
-  long long pitch = 1;
-  long long step[DIM];
-#pragma unroll
-  for (int d = DIM - 1; d >= 0; --d) {
-    step[d] = pitch;
-    pitch *= shape[3 - DIM + d];
-  }
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) {
-    const int len = shape[3 - DIM + d];
-    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
-    const double fl = floor(c[d]);
-    const double t = c[d] - fl;
-    w[d][0] = 1.0 - t;
-    w[d][1] = 1.0 - w[d][0];
-    base[d] = static_cast<long long>(fl);
-  }
-  double acc = 0.0;
-#pragma unroll
-  for (int tap = 0; tap < (1 << DIM); ++tap) {
-    long long idx = 0;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      const int bit = (tap >> (DIM - 1 - d)) & 1;
-      const int len = shape[3 - DIM + d];
-      long long i = base[d] + bit;
-      if (i > len - 1) i = len > 1 ? len - 2 : 0;
-      idx += i * step[d];
-    }
-    double coeff = static_cast<double>(a[idx]);
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) coeff = coeff * w[d][(tap >> (DIM - 1 - d)) & 1];
-    acc = acc + coeff;
-  }
-  return acc;
-}
-
-template <int DIM, typename T>
-__device__ __forceinline__ double nearest_sample(const T* __restrict__ a, const int* shape,
-                                                 const double* c) {
-  long long idx = 0, pitch = 1;
-#pragma unroll
-  for (int d = DIM - 1; d >= 0; --d) {
-    const int len = shape[3 - DIM + d];
-    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
-    long long i = static_cast<long long>(floor(c[d] + 0.5));
-    i = i > len - 1 ? len - 1 : i;
-    idx += i * pitch;
-    pitch *= len;
-  }
-  return static_cast<double>(a[idx]);
-}
-
-// double -> output type like NI's CASE_INTERP_OUT_*: unsigned types add 0.5 to
-// positive values, clip and truncate; floats are narrowed.
-template <typename T>
-__device__ __forceinline__ T nd_convert(double v, double vmax) {
-  v = v > 0.0 ? v + 0.5 : 0.0;
-  v = v > vmax ? vmax : v;
-  return static_cast<T>(v);
-}
-template <>
-__device__ __forceinline__ float nd_convert<float>(double v, double) {
-  return static_cast<float>(v);
-}
-
 template <int DIM, typename T>
 __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
   const long long n = (long long)a.oshape[0] * a.oshape[1] * a.oshape[2];
@@ -292,12 +218,12 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
   double dense[DIM];
 #pragma unroll
   for (int d = 0; d < DIM; ++d)
-    dense[d] = linear_sample<DIM, double>(a.map + (long long)(DIM - 1 - d) * nodes, a.mshape, pos);
+    dense[d] = sfm::linear_sample<DIM>(a.map + (long long)(DIM - 1 - d) * nodes, a.mshape, pos);
   const T* img = static_cast<const T*>(a.image);
-  const double v = a.order == 0 ? nearest_sample<DIM, T>(img, a.ishape, dense)
-                                : linear_sample<DIM, T>(img, a.ishape, dense);
+  const double v = a.order == 0 ? sfm::nearest_sample<DIM>(img, a.ishape, dense)
+                                : sfm::linear_sample<DIM>(img, a.ishape, dense);
   constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
-  static_cast<T*>(a.out)[i] = nd_convert<T>(v, vmax);
+  static_cast<T*>(a.out)[i] = sfm::nd_convert<T>(v, vmax);
 }
 
 }  // namespace
@@ -348,6 +274,153 @@ extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) {
     default: return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: dtype %d", d->dtype);
   }
 #undef SFM_NDW
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// processor/warp.py: StitchAndRender3dTiles.process (:292-343): per tile two
+// ndimage_warp calls (image, blend weights) and a float32 weighted sum, then
+// the normalisation and the cast -- here one kernel per output box.  A
+// workgroup takes a brick of kBrickY lines of kBrickX voxels in one z plane
+// (one wave per line, so stores are whole lines), walks the tile table in
+// ascending order, drops a tile whose sub_box misses the brick (a test on
+// block indices and table entries only: a scalar branch) and only then tests
+// its own voxel.  The dense coordinates are computed once per (voxel, tile)
+// and serve both samples; img and norm live in registers.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kBrickX = 64, kBrickY = 4;
+
+struct RenderArgs {
+  const SfmRenderTile* tiles;
+  void* out;
+  int n_tiles, order;
+  int oshape[3];
+  double stride[3];
+};
+
+// NumPy's astype from float32: integers truncate toward zero
+template <typename O>
+__device__ __forceinline__ O render_cast(float v) {
+  return static_cast<O>(static_cast<int>(v));
+}
+template <>
+__device__ __forceinline__ float render_cast<float>(float v) {
+  return v;
+}
+
+template <typename T, typename O>
+__global__ void __launch_bounds__(kBrickX* kBrickY) render_tiles_kernel(RenderArgs a) {
+  const int bx0 = blockIdx.x * kBrickX, by0 = blockIdx.y * kBrickY;
+  const int bx1 = min(bx0 + kBrickX, a.oshape[2]), by1 = min(by0 + kBrickY, a.oshape[1]);
+  const int z = blockIdx.z;
+  const int x = bx0 + threadIdx.x, y = by0 + threadIdx.y;
+  const bool live = x < bx1 && y < by1;
+  constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
+  float img = 0.f, norm = 0.f;
+  for (int t = 0; t < a.n_tiles; ++t) {
+    const SfmRenderTile& r = a.tiles[t];
+    // the brick against sub_box
+    const int sz = r.sub_start[0], sy = r.sub_start[1], sx = r.sub_start[2];
+    const int ez = sz + r.sub_size[0], ey = sy + r.sub_size[1], ex = sx + r.sub_size[2];
+    if (z < sz || z >= ez || by1 <= sy || by0 >= ey || bx1 <= sx || bx0 >= ex) continue;
+    // the voxel against sub_box
+    if (!live || y < sy || y >= ey || x < sx || x >= ex) continue;
+    // node-space position (warp.py:305), o relative to local_warp_box
+    const int o[3] = {z - sz, y - sy, x - sx};
+    double pos[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) pos[d] = (static_cast<double>(o[d]) - r.offset[d]) / a.stride[d];
+    // dense coordinates z, y, x = channels 2, 1, 0 of the absolute map (warp.py:308-311)
+    const long long nodes = (long long)r.map_shape[0] * r.map_shape[1] * r.map_shape[2];
+    double dense[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const sfm::ShiftedMap m = {r.abs_map + (long long)(2 - d) * nodes, r.shift[2 - d]};
+      dense[d] = sfm::linear_sample<3>(m, r.map_shape, pos);
+    }
+    // the image region data_box, read in place
+    const long long ipitch[3] = {(long long)r.tile_shape[1] * r.tile_shape[2], r.tile_shape[2], 1};
+    const long long wpitch[3] = {0, r.tile_shape[2], 1};
+    const long long worg = (long long)r.data_start[1] * r.tile_shape[2] + r.data_start[2];
+    const T* im = static_cast<const T*>(r.image) + r.data_start[0] * ipitch[0] + worg;
+    const double v = a.order == 0 ? sfm::nearest_sample<3>(im, r.data_size, dense, ipitch)
+                                  : sfm::linear_sample<3>(im, r.data_size, dense, ipitch);
+    const T iv = sfm::nd_convert<T>(v, vmax);
+    // the weights: the 2-D array repeated over data_size[0] planes, order 1
+    const float w = sfm::nd_convert<float>(
+        sfm::linear_sample<3>(r.weights + worg, r.data_size, dense, wpitch), 0.0);
+    img = img + static_cast<float>(iv) * w;
+    norm = norm + w;
+  }
+  if (!live) return;
+  if (norm > 0.f) img = img / norm;
+  static_cast<O*>(a.out)[((long long)z * a.oshape[1] + y) * a.oshape[2] + x] = render_cast<O>(img);
+}
+
+}  // namespace
+
+extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
+  if (!d || !d->out) return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: NULL argument");
+  if (d->n_tiles < 0) return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: n_tiles %d", d->n_tiles);
+  if (d->n_tiles > 0 && (!d->tiles || !d->tiles_host))
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: NULL tile table");
+  if (d->order != 0 && d->order != 1)
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: interpolation order %d (0 and 1 are built)",
+                     d->order);
+  if (d->dtype != SFM_DTYPE_U8 && d->dtype != SFM_DTYPE_U16 && d->dtype != SFM_DTYPE_F32)
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: dtype %d", d->dtype);
+  if (d->out_dtype != d->dtype && d->out_dtype != SFM_DTYPE_F32)
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: out_dtype %d for tiles of dtype %d",
+                     d->out_dtype, d->dtype);
+  RenderArgs a;
+  a.tiles = d->tiles;
+  a.out = d->out;
+  a.n_tiles = d->n_tiles;
+  a.order = d->order;
+  for (int k = 0; k < 3; ++k) {
+    if (d->out_shape[k] < 1) return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: bad out_shape");
+    if (!(d->stride[k] != 0.0)) return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: stride");
+    a.oshape[k] = d->out_shape[k];
+    a.stride[k] = d->stride[k];
+  }
+  // every box of the table lies inside the array it indexes
+  for (int t = 0; t < d->n_tiles; ++t) {
+    const SfmRenderTile& r = d->tiles_host[t];
+    if (!r.image || !r.abs_map || !r.weights)
+      return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: tile %d: NULL array", t);
+    for (int k = 0; k < 3; ++k) {
+      if (r.tile_shape[k] < 1 || r.map_shape[k] < 1 || r.data_size[k] < 1 || r.sub_size[k] < 1)
+        return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: tile %d: bad shape", t);
+      if (r.data_start[k] < 0 ||
+          (long long)r.data_start[k] + r.data_size[k] > r.tile_shape[k])
+        return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: tile %d: data_box leaves the tile", t);
+      if (r.sub_start[k] < 0 || (long long)r.sub_start[k] + r.sub_size[k] > d->out_shape[k])
+        return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: tile %d: sub_box leaves the output", t);
+    }
+  }
+  const long long gx = (a.oshape[2] + kBrickX - 1) / kBrickX;
+  const long long gy = (a.oshape[1] + kBrickY - 1) / kBrickY;
+  if (gy > 65535 || a.oshape[0] > 65535)
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: too large");
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  const dim3 g(static_cast<unsigned>(gx), static_cast<unsigned>(gy),
+               static_cast<unsigned>(a.oshape[0])), b(kBrickX, kBrickY);
+#define SFM_RT(T)                                                         \
+  do {                                                                    \
+    if (d->out_dtype == d->dtype)                                         \
+      hipLaunchKernelGGL((render_tiles_kernel<T, T>), g, b, 0, st, a);    \
+    else                                                                  \
+      hipLaunchKernelGGL((render_tiles_kernel<T, float>), g, b, 0, st, a); \
+  } while (0)
+  switch (d->dtype) {
+    case SFM_DTYPE_U8: SFM_RT(unsigned char); break;
+    case SFM_DTYPE_U16: SFM_RT(unsigned short); break;
+    default: SFM_RT(float); break;
+  }
+#undef SFM_RT
   SFM_LAUNCH_CHECK();
   return SFM_OK;
 }
