@@ -99,6 +99,9 @@ int sfm_device_count(int* count);
  *                         time (default 8)
  *   SFM_MFMA_PRIO=n       wave priority experiment (0..3)
  *   SFM_MFMA_MAX_WG_PER_CU=n   occupancy cap of the correlation kernel
+ *   SFM_MFMA_GUARD_2R=1   lazy / pruned path: the row band around hot rows and pruned tiles
+ *                         is 2 x peak_radius rows everywhere (default: the rows the peak
+ *                         kernels can read -- the clamped window and min_distance)
  *   SFM_MASKED_FAST=0     masked patches always take all eight passes
  *   SFM_MASKED_DEADROWS=0 no overlap-rule skips in the masked assembly
  *   SFM_MASKED_GROUPS=n   masked matrix-core path: reference batches (`group` patches each)

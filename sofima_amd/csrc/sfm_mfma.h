@@ -262,7 +262,7 @@ struct MfmaArgs {
   long long* clk;
   int prio_mode;      // experiment knob: 0 natural, 1 alternate per tile, 2 static
   // exact pruning of dy tiles (fused-peaks mode): tbound[b][p] bounds |surface|
-  // over tile p widened by `guard` rows (prep output; see the tile loop)
+  // over tile p widened by tile_guard(p) rows (prep output; see the tile loop)
   float* tbound;      // [batch, kBoundStride]; the last two entries: outer column tiles
   int prune;
   int touch_all;      // lazy modes: pull the whole correction table into L2, not only the requested tiles' rows (SFM_MFMA_TOUCH_ALL=1)
@@ -271,6 +271,13 @@ struct MfmaArgs {
   int count_tiles;    // report the pruning counts through clk (timing hooks on)
   int probe;          // seed the running maximum from a probe block (see the kernel)
   int guard, guard_x;
+  // The row band in exact terms (need_tiles / tile_guard below): the first peak's
+  // sharpness window is win = min(2 peak_radius + 1, Sy) rows tall and starts at
+  // clamp(row - win / 2, 0, win_top), win_top = Sy - win; the max filter reads
+  // guard_md = min_distance rows either side of a hot element.  `guard` (twice the
+  // radius) is what a window pushed back inside the surface can reach: it stays
+  // the band of the tiles under such a window, and all there is along x.
+  int win, win_top, guard_md;
   // Correction table built where it is read (kModeSameExactLazyG): the prep kernel
   // leaves, instead of G, the centred column sums above every 16th patch row --
   // c16[side][I][x] = sum_{y < 16 I} (pixel[y][x] - centre), I <= Py / 16, ints (and
@@ -283,6 +290,31 @@ struct MfmaArgs {
   int nq;             // column tiles of the kernel variant
   int prune_k[4];     // outer column tiles (each side) of the row-loop variants (ascending)
 };
+
+// Row tiles [*lo_t, *hi_t] that must be in memory when the rows [r_lo, r_hi] of the
+// surface may hold hot elements: what the peak kernels can read on their account
+// is the sharpness window of a first peak in one of these rows (its start is
+// monotone in the row, so the two ends cover the rows between) and the max-filter
+// rows of every hot element.  Scalar when its arguments are.
+__device__ __forceinline__ void need_tiles(const MfmaArgs& a, int r_lo, int r_hi, int* lo_t,
+                                           int* hi_t) {
+  const int w_lo = min(max(r_lo - (a.win >> 1), 0), a.win_top);
+  const int w_hi = min(max(r_hi - (a.win >> 1), 0), a.win_top) + a.win - 1;
+  const int lo = max(min(w_lo, r_lo - a.guard_md), 0);
+  const int hi = min(max(w_hi, r_hi + a.guard_md), a.win_top + a.win - 1);
+  *lo_t = lo >> 4;
+  *hi_t = min(hi >> 4, a.n_order - 1);
+}
+
+// A-priori pruning: the rows around row tile p whose elements must all be cold
+// before the tile may be left out.  A tile that a window pushed back inside the
+// surface can cover (it touches the first or the last `win` rows) is read from up
+// to `guard` rows away; any other tile from a hot element within guard_md rows or
+// a first peak within win / 2.
+__device__ __forceinline__ int tile_guard(const MfmaArgs& a, int p) {
+  const int t0 = 16 * p, t1 = min(16 * p + 15, a.S[0] - 1);
+  return (t0 <= a.win - 1 || t1 >= a.win_top) ? a.guard : max(a.guard_md, a.win >> 1);
+}
 
 // 16 image bytes at an arbitrary byte offset (global memory takes unaligned
 // dwordx4 loads); only the last bytes of the image need the guarded path.
@@ -391,15 +423,18 @@ constexpr int kModeGeneral = 0, kModeSame = 1, kModeRaw = 2, kModeSameExact = 3;
 // 11 x 11 sharpness window of the first peak, the hot elements themselves.  A
 // row tile is therefore stored only if it may hold a hot element (its maximum
 // exceeds threshold_rel x the running maximum, the test that also feeds the hot
-// list) or lies within the guard band (max(min_distance, 2 peak_radius) rows) of
-// a tile that may.  A tile learns that it is needed from a request mask in LDS
-// if the hot neighbour finished first; if it had already finished without
-// storing, it is recomputed at the end of the patch (redo mask; rare, because
+// list) or holds a row that the peak kernels can read on account of a hot row of
+// such a tile (need_tiles: the clamped sharpness window of a first peak there and
+// min_distance rows either side; 5 rows for the defaults, up to 2 peak_radius only
+// next to the surface border).  A tile learns that it is needed from a request
+// mask in LDS if the hot neighbour finished first; if it had already finished
+// without storing, it is recomputed at the end of the patch (redo mask; rare, because
 // tiles are drawn innermost first and the peak sits there).  What is left
-// un-stored has the property of a pruned tile -- every element of the tile and
-// of its guard band is below threshold_rel x the final maximum -- and goes into
-// the same skip mask for the overflow sweeps of the peak kernels.  Values and
-// decisions that reach the output are unchanged: bit-identical results.
+// un-stored has the property of a pruned tile -- no element of it is above
+// threshold_rel x the final maximum, none is within min_distance rows of one that
+// is, none lies in the first peak's window -- and goes into the same skip mask
+// for the overflow sweeps of the peak kernels.  Values and decisions that reach
+// the output are unchanged: bit-identical results.
 constexpr int kModeSameLazy = 4, kModeSameExactLazy = 5;
 // kModeSameExactLazy with the correction table built in the epilogue of the tiles
 // that are stored (chosen by choose_mode; Py a multiple of 16): no table G in memory.

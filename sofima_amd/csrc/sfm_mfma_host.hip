@@ -267,6 +267,17 @@ void fill_peaks(const SfmXcorrDesc* d, const sfm::FusedPeaks& fp, bool same, con
   a.skipmask = fp.skipmask;
   a.guard = std::max(d->min_distance, 2 * d->peak_radius[1]);
   a.guard_x = std::max(d->min_distance, 2 * d->peak_radius[2]);
+  // rows: the sharpness window as peaks_second_kernel places it, and the max filter
+  a.win = std::min(2 * std::max(d->peak_radius[1], 0) + 1, a.S[0]);
+  a.win_top = a.S[0] - a.win;
+  a.guard_md = d->min_distance;
+  if (sfm::measure_option_tri("SFM_MFMA_GUARD_2R") == 1) {
+    // the band as it was: `guard` rows around every hot row and every tile (a
+    // window of one row and a max filter of `guard` rows ask for exactly that)
+    a.win = 1;
+    a.win_top = a.S[0] - 1;
+    a.guard_md = a.guard;
+  }
   a.nq = v.nca + v.nce - 1;
   a.prune_k[0] = col_skip_lo(a.nq);
   a.prune_k[1] = col_skip_hi(a.nq);

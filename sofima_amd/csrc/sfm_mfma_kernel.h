@@ -493,7 +493,8 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
         // recomputed: measured 2.4 redone tiles per patch without any request,
         // 0.75 with the peak tile's band alone -- the peak's blob often straddles
         // two tiles, whose bands are four tiles)
-        const int pt = *best_lds >> 8, gt = (a.guard + 15) >> 4;
+        // (a prediction: the band of a tile away from the surface border, in tiles)
+        const int pt = *best_lds >> 8, gt = (max(a.guard_md, a.win >> 1) + 15) >> 4;
         const int lo_t = max(pt - gt, 0), hi_t = min(pt + gt, a.n_order - 1);
         const int pv = *lz_prev;
         // (the band of the peak tile only while there is no previous need mask: the
@@ -636,10 +637,10 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
         const int hq_hi = *const_cast<volatile int*>(&lz_cq[1]);
         int mask_l = 0;
         if (mine && tm_l > thr_f) {
-          // (the guard band is counted in rows from the tile's hot rows: 10 rows
-          // reach both neighbouring tiles from a quarter of the positions only)
-          const int lo_t = max(16 * t_l + (rr_l & 255) - a.guard, 0) >> 4;
-          const int hi_t = min((16 * t_l + (rr_l >> 8) + a.guard) >> 4, a.n_order - 1);
+          // (the band is counted in rows from the tile's hot rows, and is what the
+          // peak kernels can read on their account: need_tiles)
+          int lo_t, hi_t;
+          need_tiles(a, 16 * t_l + (rr_l & 255), 16 * t_l + (rr_l >> 8), &lo_t, &hi_t);
           mask_l = static_cast<int>(((2u << hi_t) - 1u) & ~((1u << lo_t) - 1u));
         }
         const int need = wave_or(mask_l);
@@ -715,11 +716,14 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
       float hd_corr = 0.f, hd_thr = 0.f;
       int hd_req = 0, hd_cq = 0;
       if (SAME && a.prune && !forced) {
-        // Exact pruning.  Every element of this tile and of the `guard` rows
+        // Exact pruning.  Every element of this tile and of the tile_guard(p) rows
         // around it is bounded by tb (prep kernel).  If tb < threshold_rel x (the
         // running maximum, which never exceeds the final one), none of them is
-        // the maximum, a peak candidate, inside a candidate's max-filter window
-        // or inside the first peak's sharpness window: the tile is never read
+        // the maximum or a peak candidate, so no row of the tile is inside a
+        // candidate's max-filter window (min_distance <= tile_guard) or inside the
+        // first peak's sharpness window (a window centred on its peak reaches
+        // peak_radius <= tile_guard rows; one pushed back inside the surface covers
+        // only the tiles that keep the full 2 peak_radius): the tile is never read
         // for its values.  It is not stored at all; the overflow fall-backs of the
         // peak kernels, which sweep whole surfaces, get the set of pruned tiles
         // (a.skipmask) and skip / zero them.
@@ -1912,14 +1916,14 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
         if constexpr (LAZY) {
           // Store this tile?  `hot`: it may hold an element above threshold_rel x
           // the final maximum (the running maximum only grows, so this errs on the
-          // side of storing).  A hot tile asks for the tiles of its guard band; a
+          // side of storing).  A hot tile asks for the tiles of its band; a
           // tile of the band that had finished before is dealt with at the end of
           // the patch, against the FINAL maximum (redo phase above).
           const bool hot = tmax > thr_t;
           int nbmask = 0;
           if (hot) {
-            // rows of the tile that hold a possibly hot element -> the tiles within
-            // `guard` rows of them
+            // rows of the tile that hold a possibly hot element -> the tiles the peak
+            // kernels can read because of them (need_tiles)
             unsigned rowmask = 0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1933,8 +1937,8 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
             }
             const int r_lo = __builtin_ctz(rowmask | 0x10000u);
             const int r_hi = 31 - __builtin_clz(rowmask | 1u);
-            const int lo_t = max(16 * p + r_lo - a.guard, 0) >> 4;
-            const int hi_t = min((16 * p + r_hi + a.guard) >> 4, a.n_order - 1);
+            int lo_t, hi_t;
+            need_tiles(a, 16 * p + r_lo, 16 * p + r_hi, &lo_t, &hi_t);
             nbmask = static_cast<int>(((2u << hi_t) - 1u) & ~((1u << lo_t) - 1u)) | (1 << p);
             if (lane == 0) lz_rows[p] = r_lo | (r_hi << 8);
           }

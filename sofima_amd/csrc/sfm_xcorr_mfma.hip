@@ -933,15 +933,20 @@ __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
     // |surface[dy][dx]| = |sum over the overlap of (a - mean_a)(b - mean_b)|
     //   <= sqrt(E_A(rows of the overlap) E_B(rows of the overlap))     (Cauchy-Schwarz,
     // the column range only shrinks the sums), and the row sets are nested in
-    // |dy|: the bound of a tile widened by `guard` rows is the one of its row
-    // nearest the centre.  (row_pre was finished before the barrier of phase 3a.)
+    // |dy|: the bound of a tile widened by g rows is the one of its row nearest
+    // the centre.  g = tile_guard(p): the rows from which a hot element or the
+    // first peak's window can make the peak kernels read the tile -- min_distance
+    // and peak_radius rows, 2 peak_radius only for the tiles under a window that
+    // the surface border pushed back.  (row_pre was finished before the barrier
+    // of phase 3a.)
     const int p = threadIdx.x;
     const int lo = 16 * p - (py - 1), hi = min(lo + 15, py - 1);
     float bound = INFINITY;  // tiles that do not exist are never asked for
     if (lo <= py - 1) {
+      const int g = tile_guard(a, p);
       int d = 0;
-      if (lo > 0) d = max(0, lo - a.guard);
-      if (hi < 0) d = min(0, hi + a.guard);
+      if (lo > 0) d = max(0, lo - g);
+      if (hi < 0) d = min(0, hi + g);
       // out[dy] = sum_yb a[yb + dy] b[yb]:  dy >= 0: a rows [dy, py), b rows [0, py - dy)
       const double ea = d >= 0 ? row_pre[0][py] - row_pre[0][d] : row_pre[0][py + d];
       const double eb = d >= 0 ? row_pre[1][py - d] : row_pre[1][py] - row_pre[1][-d];
@@ -1047,9 +1052,10 @@ __device__ __forceinline__ void prep_same_body(const MfmaArgs& a, const int b,
     };
     const int p = lane >> 1, side = lane & 1;
     const int lo = 16 * p - (py - 1), hi = min(lo + 15, py - 1);
+    const int g = tile_guard(a, p);   // (rows; along x the band stays guard_x)
     int dyy = 0;
-    if (lo > 0) dyy = max(0, lo - a.guard);
-    if (hi < 0) dyy = min(0, hi + a.guard);
+    if (lo > 0) dyy = max(0, lo - g);
+    if (hi < 0) dyy = min(0, hi + g);
     // out[dy][dx] = sum a[yb + dy][xa] b[yb][xa - dx]
     const int ra0 = dyy >= 0 ? dyy : 0, ra1 = dyy >= 0 ? py : py + dyy;
     const int rb0 = dyy >= 0 ? 0 : -dyy, rb1 = dyy >= 0 ? py - dyy : py;

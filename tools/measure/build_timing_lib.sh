@@ -4,7 +4,7 @@
 # = the units of the matrix-core correlation path with clock64 phase ticks + device printf
 # (-DSFM_MFMA_TIMING) and the
 # measurement-only switches (-DSFM_MEASUREMENT_SWITCHES: SFM_MFMA_PROBE / TOUCH_ALL / EXACT /
-# QUEUE / PRIO / MAX_WG_PER_CU, which the production library ignores).  Built here, on the CPU
+# QUEUE / PRIO / MAX_WG_PER_CU / GUARD_2R, which the production library ignores).  Built here, on the CPU
 # box -- it travels with gpurun.  NOTIMING=1: the switches without the ticks
 # (libsofima_amd_measure.so: production timing behaviour, for A/B runs and the identity tests
 # of those switches).
