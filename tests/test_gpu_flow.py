@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from oracle import flow_oracle
+from tests import masked_exact_ref
 from tests.util import check_flow, check_sharpness, em_texture
 
 pytestmark = pytest.mark.gpu
@@ -949,7 +950,13 @@ def test_masked_paths_random_geometry_fuzz(gpu, seed):
   # MFMA path must be the closest, the f32 direct kernel and the f32 FFT form
   # carry float32 accumulation error of un-centred 8-bit data
   ref = flow_oracle.xcorr_surface(prev, curr, pm, cm, dtype=np.float64)
-  for method, atol in ((2, 5e-5), (3, 2e-3), (1, 2e-3)):
+  # the matrix-core path: EVERY element against the exact sums (its products are
+  # exact integers, so neither cut leaves it an excuse: tests/masked_exact_ref.py)
+  got = flow_field.masked_xcorr(prev.astype(np.uint8), curr.astype(np.uint8), pm, cm, method=2)
+  exact = masked_exact_ref.classify(masked_exact_ref.terms(prev, curr, pm, cm), None,
+                                    masked_exact_ref.BAND_MFMA)
+  masked_exact_ref.check(got, exact, masked_exact_ref.ATOL_MFMA)
+  for method, atol in ((3, 2e-3), (1, 2e-3)):
     got = flow_field.masked_xcorr(prev.astype(np.uint8), curr.astype(np.uint8), pm, cm,
                                   method=method)
     assert got.shape == ref.shape
@@ -1118,11 +1125,15 @@ def test_masked_clean_patch_shortcut_is_bit_identical(gpu, monkeypatch, py, px, 
       [curr[k][~cm[k]].mean(dtype=np.float64) for k in range(len(curr))],
       np.float32)[:, None, None]
   want = flow_oracle.xcorr_surface(a0, b0, pm, cm, dtype=np.float64, workers=4)
-  # elements whose denominator sits at the tolerance may flip to 0 on one side
-  flipped = (fast == 0) != (want == 0)
-  assert flipped.mean() < 1e-3, flipped.mean()
-  bad = (np.abs(fast - want) > 3e-5) & ~flipped
-  assert bad.mean() < 2e-5, (bad.mean(), np.abs(fast - want)[bad].max())
+  # every element against the exact sums: cut elements are 0, kept ones within
+  # 2^-19, either only where the exact denominator is within 2^-18 of the tolerance
+  exact = masked_exact_ref.classify(masked_exact_ref.terms(prev, curr, pm, cm), None,
+                                    masked_exact_ref.BAND_MFMA)
+  masked_exact_ref.check(fast, exact, masked_exact_ref.ATOL_MFMA)
+  # (and the float64 FFT restatement agrees with those sums wherever both decide alike)
+  same = (exact['want'] == 0) == (want == 0)
+  assert same.mean() > 1 - 1e-3
+  assert np.abs(want - exact['want'])[same].max() < 3e-5
   # all patches clean / all dirty / one-sided mask arrays
   none = np.zeros_like(pm)
   for masks in ((none, np.zeros_like(cm)), (pm, None), (None, cm)):
@@ -1131,6 +1142,9 @@ def test_masked_clean_patch_shortcut_is_bit_identical(gpu, monkeypatch, py, px, 
     monkeypatch.delenv('SFM_MASKED_FAST')
     fast = flow_field.masked_xcorr(prev, curr, masks[0], masks[1], mean=None)
     np.testing.assert_array_equal(fast, eight)
+    exact = masked_exact_ref.classify(masked_exact_ref.terms(prev, curr, *masks), None,
+                                      masked_exact_ref.BAND_MFMA)
+    masked_exact_ref.check(fast, exact, masked_exact_ref.ATOL_MFMA)
 
 
 @pytest.mark.parametrize('p', [64, 160, 48])
