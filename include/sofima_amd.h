@@ -41,8 +41,10 @@ extern "C" {
                                    sfm_affine_map and sfm_warp_points were added
                                    without a bump: new entry points only, no
                                    existing struct or call changed; likewise
-                                   sfm_prev_state, sfm_mask_irregular_f64 and
-                                   sfm_render_tiles3d */
+                                   sfm_prev_state, sfm_mask_irregular_f64,
+                                   sfm_render_tiles3d, and sfm_spline_prefilter,
+                                   sfm_ndimage_warp_spline and
+                                   sfm_render_tiles3d_spline */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -714,6 +716,58 @@ typedef struct SfmRenderTilesDesc {
 } SfmRenderTilesDesc;
 
 int sfm_render_tiles3d(const SfmRenderTilesDesc* desc);
+
+/* ------------------------------------------------------------------------
+ * Spline orders 2 .. 5 of the two calls above (sfm_spline.hip, sfm_warp.hip).
+ * SciPy samples orders above 1 from B-spline coefficients, not from the image:
+ * scipy.ndimage.spline_filter(image, order, output=float64, mode="constant"),
+ * a recursive filter along axis 0, then 1, then 2, each pass on the previous
+ * pass's output, mirror boundaries, axes of length 1 skipped.
+ * sfm_spline_prefilter computes these coefficients for a table of arrays (or
+ * regions of arrays) in one batch of launches: plain double arithmetic in
+ * SciPy's operation order, one thread per line (a line's recursion is not
+ * split: that would change the rounding), the x pass staged through LDS.  The
+ * poles are SciPy's literals and live in the library; pow(pole, len - 1) of
+ * the mirror initialisation is NOT computed on the device, whose pow is not
+ * libm's: the caller fills `zn` with the host's libm.
+ * ---------------------------------------------------------------------- */
+typedef struct SfmSplineItem {
+  const void* image;            /* device: first element of the region         */
+  int64_t pitch[3];             /* z, y, x element distance within image       */
+  int64_t coeff_offset;         /* element offset within coeffs of this item's
+                                   dense [shape] float64 coefficients          */
+  int32_t shape[3];             /* z, y, x of the region; 2-D: shape[0] = 1    */
+  int32_t reserved;             /* 0                                           */
+  double zn[3][2];              /* pow(pole p, shape[k] - 1) per axis k and
+                                   pole p (order 2, 3: p = 0 only), host libm  */
+} SfmSplineItem;
+
+typedef struct SfmSplinePrefilterDesc {
+  int32_t dtype;                /* SFM_DTYPE_U8 | U16 | F32 of every image     */
+  int32_t order;                /* 2 .. 5                                      */
+  int32_t n_items;              /* entries of the table, >= 0                  */
+  int32_t reserved;             /* 0                                           */
+  const SfmSplineItem* items_host;  /* host copy of the table, checked here    */
+  const SfmSplineItem* items;   /* device copy of the same table               */
+  double* coeffs;               /* device, caller-owned: coeffs_len doubles    */
+  int64_t coeffs_len;           /* every item lies inside [0, coeffs_len)      */
+  void* stream;
+} SfmSplinePrefilterDesc;
+
+int sfm_spline_prefilter(const SfmSplinePrefilterDesc* desc);
+
+/* sfm_ndimage_warp with order 2 .. 5: desc->image holds the float64 B-spline
+ * coefficients of the image (dense, image_shape), desc->dtype is the type of
+ * `out` alone.  The dense coordinates stay order 1. */
+int sfm_ndimage_warp_spline(const SfmNdWarpDesc* desc);
+
+/* sfm_render_tiles3d with order 2 .. 5 for the image (the weights stay order
+ * 1).  The reference warps each tile's data_box CROP, so the spline is that of
+ * the crop, mirrored at the crop's edges: `coeffs` holds the float64
+ * coefficients of the data_box regions of all table entries, each dense in its
+ * data_size, back to back in table order (sfm_spline_prefilter with one item
+ * per entry); `image` of an entry is not read. */
+int sfm_render_tiles3d_spline(const SfmRenderTilesDesc* desc, const double* coeffs);
 
 /* ------------------------------------------------------------------------
  * Map geometry: the one-pass helpers that the reference's renderers call

@@ -327,6 +327,31 @@ class SfmRenderTilesDesc(C.Structure):
   ]
 
 
+class SfmSplineItem(C.Structure):
+  _fields_ = [
+      ('image', C.c_void_p),
+      ('pitch', C.c_int64 * 3),
+      ('coeff_offset', C.c_int64),
+      ('shape', i32 * 3),
+      ('reserved', i32),
+      ('zn', (C.c_double * 2) * 3),
+  ]
+
+
+class SfmSplinePrefilterDesc(C.Structure):
+  _fields_ = [
+      ('dtype', i32),
+      ('order', i32),
+      ('n_items', i32),
+      ('reserved', i32),
+      ('items_host', C.POINTER(SfmSplineItem)),
+      ('items', C.c_void_p),
+      ('coeffs', C.c_void_p),
+      ('coeffs_len', C.c_int64),
+      ('stream', C.c_void_p),
+  ]
+
+
 SHIFT_TO_ABSOLUTE = 0
 SHIFT_TO_RELATIVE = 1
 EXTENTS_OUTER = 0
@@ -597,6 +622,9 @@ SIGNATURES = {
     'sfm_warp_section': (C.c_int, [C.POINTER(SfmWarpDesc)]),
     'sfm_ndimage_warp': (C.c_int, [C.POINTER(SfmNdWarpDesc)]),
     'sfm_render_tiles3d': (C.c_int, [C.POINTER(SfmRenderTilesDesc)]),
+    'sfm_spline_prefilter': (C.c_int, [C.POINTER(SfmSplinePrefilterDesc)]),
+    'sfm_ndimage_warp_spline': (C.c_int, [C.POINTER(SfmNdWarpDesc)]),
+    'sfm_render_tiles3d_spline': (C.c_int, [C.POINTER(SfmRenderTilesDesc), C.c_void_p]),
     'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),
     'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
     'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),

@@ -40,6 +40,7 @@ SOURCES = {
     'sfm_invmap.hip': ['-ffp-contract=off'],
     'sfm_comm.hip': [],
     'sfm_warp.hip': ['-ffp-contract=off'],
+    'sfm_spline.hip': ['-ffp-contract=off'],
     'sfm_mapgeom.hip': ['-ffp-contract=off'],
 }
 # SFM_BUILD_FLAGS: extra flags for every unit (-DSFM_MEASUREMENT_SWITCHES: the library

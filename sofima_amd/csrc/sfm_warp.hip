@@ -183,8 +183,9 @@ extern "C" int sfm_warp_section(const SfmWarpDesc* d) {
 // ---------------------------------------------------------------------------
 // warp.ndimage_warp (warp.py:189-335): scipy.ndimage.map_coordinates twice --
 // order 1 on the float64 source map at the node-space position of the output
-// voxel, then order 0 / 1 on the image at the resulting coordinates.  Double
-// arithmetic in SciPy's order (this file is built with -ffp-contract=off).
+// voxel, then order 0 / 1 on the image at the resulting coordinates, or order
+// 2 .. 5 on its B-spline coefficients (sfm_spline_prefilter).  Double arithmetic
+// in SciPy's order (this file is built with -ffp-contract=off).
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -197,7 +198,9 @@ struct NdWarpArgs {
   double stride[3], offset[3];
 };
 
-template <int DIM, typename T>
+// ORDER 0: a.order (0 or 1) on the image; ORDER 2 .. 5: a.image holds the float64
+// B-spline coefficients of the image (sfm_spline_prefilter).
+template <int DIM, typename T, int ORDER = 0>
 __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
   const long long n = (long long)a.oshape[0] * a.oshape[1] * a.oshape[2];
   const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
@@ -219,21 +222,33 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
 #pragma unroll
   for (int d = 0; d < DIM; ++d)
     dense[d] = sfm::linear_sample<DIM>(a.map + (long long)(DIM - 1 - d) * nodes, a.mshape, pos);
-  const T* img = static_cast<const T*>(a.image);
-  const double v = a.order == 0 ? sfm::nearest_sample<DIM>(img, a.ishape, dense)
-                                : sfm::linear_sample<DIM>(img, a.ishape, dense);
+  double v;
+  if constexpr (ORDER >= 2) {
+    v = sfm::spline_sample<DIM, ORDER>(static_cast<const double*>(a.image), a.ishape, dense);
+  } else {
+    const T* img = static_cast<const T*>(a.image);
+    v = a.order == 0 ? sfm::nearest_sample<DIM>(img, a.ishape, dense)
+                     : sfm::linear_sample<DIM>(img, a.ishape, dense);
+  }
   constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
   static_cast<T*>(a.out)[i] = sfm::nd_convert<T>(v, vmax);
 }
 
 }  // namespace
 
-extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) {
+namespace {
+
+// the checks and the launch of sfm_ndimage_warp (orders 0, 1 on the image) and
+// sfm_ndimage_warp_spline (orders 2 .. 5 on coefficients)
+int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline) {
   if (!d || !d->image || !d->src_map || !d->out)
     return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: NULL argument");
   if (d->ndim != 2 && d->ndim != 3) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: ndim %d", d->ndim);
-  if (d->order != 0 && d->order != 1)
+  if (!spline && d->order != 0 && d->order != 1)
     return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: interpolation order %d (0 and 1 are built)",
+                     d->order);
+  if (spline && (d->order < 2 || d->order > 5))
+    return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_spline: interpolation order %d (2 .. 5)",
                      d->order);
   NdWarpArgs a;
   a.image = d->image;
@@ -260,12 +275,22 @@ extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) {
   if (grid > 0x7fffffffLL) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: too large");
   hipStream_t st = static_cast<hipStream_t>(d->stream);
   const dim3 g(static_cast<unsigned>(grid)), b(kBlock);
-#define SFM_NDW(T)                                                                 \
+#define SFM_NDW_ORDER(T, ORDER)                                                    \
   do {                                                                             \
     if (d->ndim == 2)                                                              \
-      hipLaunchKernelGGL((ndimage_warp_kernel<2, T>), g, b, 0, st, a);             \
+      hipLaunchKernelGGL((ndimage_warp_kernel<2, T, ORDER>), g, b, 0, st, a);      \
     else                                                                           \
-      hipLaunchKernelGGL((ndimage_warp_kernel<3, T>), g, b, 0, st, a);             \
+      hipLaunchKernelGGL((ndimage_warp_kernel<3, T, ORDER>), g, b, 0, st, a);      \
+  } while (0)
+#define SFM_NDW(T)                                                                 \
+  do {                                                                             \
+    switch (spline ? d->order : 0) {                                               \
+      case 2: SFM_NDW_ORDER(T, 2); break;                                          \
+      case 3: SFM_NDW_ORDER(T, 3); break;                                          \
+      case 4: SFM_NDW_ORDER(T, 4); break;                                          \
+      case 5: SFM_NDW_ORDER(T, 5); break;                                          \
+      default: SFM_NDW_ORDER(T, 0); break;                                         \
+    }                                                                              \
   } while (0)
   switch (d->dtype) {
     case SFM_DTYPE_U8: SFM_NDW(unsigned char); break;
@@ -274,8 +299,17 @@ extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) {
     default: return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: dtype %d", d->dtype);
   }
 #undef SFM_NDW
+#undef SFM_NDW_ORDER
   SFM_LAUNCH_CHECK();
   return SFM_OK;
+}
+
+}  // namespace
+
+extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) { return ndimage_warp_launch(d, false); }
+
+extern "C" int sfm_ndimage_warp_spline(const SfmNdWarpDesc* d) {
+  return ndimage_warp_launch(d, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -295,6 +329,7 @@ constexpr int kBrickX = 64, kBrickY = 4;
 
 struct RenderArgs {
   const SfmRenderTile* tiles;
+  const double* coeffs;   // spline orders: the crops' coefficients, back to back
   void* out;
   int n_tiles, order;
   int oshape[3];
@@ -311,7 +346,10 @@ __device__ __forceinline__ float render_cast<float>(float v) {
   return v;
 }
 
-template <typename T, typename O>
+// ORDER 0: a.order (0 or 1), the data_box region of the tile read in place;
+// ORDER 2 .. 5: the region's B-spline coefficients, a.coeffs + the sizes of the
+// regions of the table entries before it.
+template <typename T, typename O, int ORDER = 0>
 __global__ void __launch_bounds__(kBrickX* kBrickY) render_tiles_kernel(RenderArgs a) {
   const int bx0 = blockIdx.x * kBrickX, by0 = blockIdx.y * kBrickY;
   const int bx1 = min(bx0 + kBrickX, a.oshape[2]), by1 = min(by0 + kBrickY, a.oshape[1]);
@@ -320,8 +358,12 @@ __global__ void __launch_bounds__(kBrickX* kBrickY) render_tiles_kernel(RenderAr
   const bool live = x < bx1 && y < by1;
   constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
   float img = 0.f, norm = 0.f;
+  long long next_region = 0;
   for (int t = 0; t < a.n_tiles; ++t) {
     const SfmRenderTile& r = a.tiles[t];
+    const long long region = next_region;
+    if constexpr (ORDER >= 2)
+      next_region += (long long)r.data_size[0] * r.data_size[1] * r.data_size[2];
     // the brick against sub_box
     const int sz = r.sub_start[0], sy = r.sub_start[1], sx = r.sub_start[2];
     const int ez = sz + r.sub_size[0], ey = sy + r.sub_size[1], ex = sx + r.sub_size[2];
@@ -345,9 +387,14 @@ __global__ void __launch_bounds__(kBrickX* kBrickY) render_tiles_kernel(RenderAr
     const long long ipitch[3] = {(long long)r.tile_shape[1] * r.tile_shape[2], r.tile_shape[2], 1};
     const long long wpitch[3] = {0, r.tile_shape[2], 1};
     const long long worg = (long long)r.data_start[1] * r.tile_shape[2] + r.data_start[2];
-    const T* im = static_cast<const T*>(r.image) + r.data_start[0] * ipitch[0] + worg;
-    const double v = a.order == 0 ? sfm::nearest_sample<3>(im, r.data_size, dense, ipitch)
-                                  : sfm::linear_sample<3>(im, r.data_size, dense, ipitch);
+    double v;
+    if constexpr (ORDER >= 2) {
+      v = sfm::spline_sample<3, ORDER>(a.coeffs + region, r.data_size, dense);
+    } else {
+      const T* im = static_cast<const T*>(r.image) + r.data_start[0] * ipitch[0] + worg;
+      v = a.order == 0 ? sfm::nearest_sample<3>(im, r.data_size, dense, ipitch)
+                       : sfm::linear_sample<3>(im, r.data_size, dense, ipitch);
+    }
     const T iv = sfm::nd_convert<T>(v, vmax);
     // the weights: the 2-D array repeated over data_size[0] planes, order 1
     const float w = sfm::nd_convert<float>(
@@ -362,14 +409,23 @@ __global__ void __launch_bounds__(kBrickX* kBrickY) render_tiles_kernel(RenderAr
 
 }  // namespace
 
-extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
+namespace {
+
+// the checks and the launch of sfm_render_tiles3d (coeffs NULL: orders 0, 1) and
+// sfm_render_tiles3d_spline (orders 2 .. 5)
+int render_tiles_launch(const SfmRenderTilesDesc* d, const double* coeffs, bool spline) {
   if (!d || !d->out) return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: NULL argument");
   if (d->n_tiles < 0) return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: n_tiles %d", d->n_tiles);
   if (d->n_tiles > 0 && (!d->tiles || !d->tiles_host))
     return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: NULL tile table");
-  if (d->order != 0 && d->order != 1)
+  if (!spline && d->order != 0 && d->order != 1)
     return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: interpolation order %d (0 and 1 are built)",
                      d->order);
+  if (spline && (d->order < 2 || d->order > 5))
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d_spline: interpolation order %d (2 .. 5)",
+                     d->order);
+  if (spline && d->n_tiles > 0 && !coeffs)
+    return sfm::fail(SFM_ERR_INVALID, "render_tiles3d_spline: NULL coefficients");
   if (d->dtype != SFM_DTYPE_U8 && d->dtype != SFM_DTYPE_U16 && d->dtype != SFM_DTYPE_F32)
     return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: dtype %d", d->dtype);
   if (d->out_dtype != d->dtype && d->out_dtype != SFM_DTYPE_F32)
@@ -377,6 +433,7 @@ extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
                      d->out_dtype, d->dtype);
   RenderArgs a;
   a.tiles = d->tiles;
+  a.coeffs = coeffs;
   a.out = d->out;
   a.n_tiles = d->n_tiles;
   a.order = d->order;
@@ -389,7 +446,7 @@ extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
   // every box of the table lies inside the array it indexes
   for (int t = 0; t < d->n_tiles; ++t) {
     const SfmRenderTile& r = d->tiles_host[t];
-    if (!r.image || !r.abs_map || !r.weights)
+    if ((!spline && !r.image) || !r.abs_map || !r.weights)
       return sfm::fail(SFM_ERR_INVALID, "render_tiles3d: tile %d: NULL array", t);
     for (int k = 0; k < 3; ++k) {
       if (r.tile_shape[k] < 1 || r.map_shape[k] < 1 || r.data_size[k] < 1 || r.sub_size[k] < 1)
@@ -408,12 +465,22 @@ extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
   hipStream_t st = static_cast<hipStream_t>(d->stream);
   const dim3 g(static_cast<unsigned>(gx), static_cast<unsigned>(gy),
                static_cast<unsigned>(a.oshape[0])), b(kBrickX, kBrickY);
-#define SFM_RT(T)                                                         \
-  do {                                                                    \
-    if (d->out_dtype == d->dtype)                                         \
-      hipLaunchKernelGGL((render_tiles_kernel<T, T>), g, b, 0, st, a);    \
-    else                                                                  \
-      hipLaunchKernelGGL((render_tiles_kernel<T, float>), g, b, 0, st, a); \
+#define SFM_RT_ORDER(T, ORDER)                                                   \
+  do {                                                                           \
+    if (d->out_dtype == d->dtype)                                                \
+      hipLaunchKernelGGL((render_tiles_kernel<T, T, ORDER>), g, b, 0, st, a);    \
+    else                                                                         \
+      hipLaunchKernelGGL((render_tiles_kernel<T, float, ORDER>), g, b, 0, st, a); \
+  } while (0)
+#define SFM_RT(T)                                                                \
+  do {                                                                           \
+    switch (spline ? d->order : 0) {                                             \
+      case 2: SFM_RT_ORDER(T, 2); break;                                         \
+      case 3: SFM_RT_ORDER(T, 3); break;                                         \
+      case 4: SFM_RT_ORDER(T, 4); break;                                         \
+      case 5: SFM_RT_ORDER(T, 5); break;                                         \
+      default: SFM_RT_ORDER(T, 0); break;                                        \
+    }                                                                            \
   } while (0)
   switch (d->dtype) {
     case SFM_DTYPE_U8: SFM_RT(unsigned char); break;
@@ -421,6 +488,17 @@ extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
     default: SFM_RT(float); break;
   }
 #undef SFM_RT
+#undef SFM_RT_ORDER
   SFM_LAUNCH_CHECK();
   return SFM_OK;
+}
+
+}  // namespace
+
+extern "C" int sfm_render_tiles3d(const SfmRenderTilesDesc* d) {
+  return render_tiles_launch(d, nullptr, false);
+}
+
+extern "C" int sfm_render_tiles3d_spline(const SfmRenderTilesDesc* d, const double* coeffs) {
+  return render_tiles_launch(d, coeffs, true);
 }

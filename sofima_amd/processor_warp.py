@@ -28,8 +28,15 @@ dense coordinate samples 0 for image and weight; with `margin > 0` a tile on the
 outer side of the grid loses its last column / row (the `-1` slice end of
 :153-155); the truncating cast after `(v * w) / w` can give `v - 1`.  Different:
 the reference adds tiles in `as_completed` order, which is unspecified; this
-code adds them in ascending tile index.  Not built: spline orders above 1,
-uint64 label tiles, `out_scale` other than 1 (NotImplementedError).
+code adds them in ascending tile index.  Spline orders 2 to 5 of the image
+(opt-in: the switch SFM_SPLINE_ORDERS=1, `_abi.set_option`; without it they raise
+NotImplementedError as before): the
+reference warps each tile's `data_box` CROP, so per `render` call the crops of
+all plan items are prefiltered into one float64 workspace (one batch of
+launches over the plan table, mirrored at the crops' edges) and the fused kernel
+samples those coefficients; orders 0 and 1 read the tiles in place.  The weights
+are always sampled with order 1.  Not built: uint64 label tiles, `out_scale`
+other than 1 (NotImplementedError).
 """
 from __future__ import annotations
 
@@ -41,6 +48,7 @@ import torch
 
 from . import _abi
 from . import _dev
+from . import _spline
 from . import map_utils
 from ._dev import DeviceArray
 
@@ -237,8 +245,7 @@ def _device_weights(w, dev) -> torch.Tensor:
 def _launch(box: Box, plan, tiles, abs_maps, weights, stride, order, out_dtype,
             device_output):
   """One sfm_render_tiles3d call over device-resident arrays (dicts by tile)."""
-  if order not in (0, 1):
-    raise NotImplementedError(f'render: interpolation order {order} (0 and 1 are built)')
+  _spline.check_order(order, 'render')
   dev = _dev.device()
   dtypes = {np.dtype(str(tiles[item[0]].dtype).replace('torch.', '')) for item in plan}
   if len(dtypes) > 1:
@@ -258,6 +265,7 @@ def _launch(box: Box, plan, tiles, abs_maps, weights, stride, order, out_dtype,
 
   stride_zyx = np.asarray(stride)
   table = (_abi.SfmRenderTile * max(len(plan), 1))()
+  regions = []
   for r, (i, data_box, tg_box, local_warp_box, sub_box) in zip(table, plan):
     data_box, tg_box = _as_box(data_box), _as_box(tg_box)
     local_warp_box, sub_box = _as_box(local_warp_box), _as_box(sub_box)
@@ -281,6 +289,14 @@ def _launch(box: Box, plan, tiles, abs_maps, weights, stride, order, out_dtype,
     r.sub_size = (C.c_int32 * 3)(*(int(v) for v in sub_box.size[::-1]))
     r.shift = (C.c_double * 3)(*(float(v) for v in shift))
     r.offset = (C.c_double * 3)(*(float(v) for v in node0))
+    if order in _spline.ORDERS:
+      # the crop the reference warps, where it lies in the tile
+      start, size = tuple(r.data_start), tuple(r.data_size)
+      if any(a < 0 or a + n > t or n < 1 for a, n, t in zip(start, size, tile.shape)):
+        raise ValueError(f'render: tile {i}: data_box {data_box} leaves the tile')
+      pitch = (tile.shape[1] * tile.shape[2], tile.shape[2], 1)
+      first = sum(a * p for a, p in zip(start, pitch))
+      regions.append((tile.data_ptr() + first * tile.element_size(), size, pitch))
 
   out_shape = tuple(int(v) for v in box.size[::-1])
   out_t = torch.empty(out_shape, dtype=_TORCH[out_dtype], device=dev)
@@ -298,7 +314,13 @@ def _launch(box: Box, plan, tiles, abs_maps, weights, stride, order, out_dtype,
     d.tiles = table_t.data_ptr()
   d.out = out_t.data_ptr()
   d.stream = _dev.stream_ptr()
-  _abi.check(_abi.load().sfm_render_tiles3d(C.byref(d)))
+  if order in _spline.ORDERS:
+    # coefficients of all crops, dense and back to back in plan order: what the
+    # kernel expects
+    coeffs, _ = _spline.prefilter(regions, _DTYPES[tile_dtype], order, dev)
+    _abi.check(_abi.load().sfm_render_tiles3d_spline(C.byref(d), coeffs.data_ptr()))
+  else:
+    _abi.check(_abi.load().sfm_render_tiles3d(C.byref(d)))
   if device_output:
     return DeviceArray(out_t)
   if out_dtype == np.uint16:
@@ -315,8 +337,9 @@ def render(box, tiles, plan, inverted, weights, stride: Sequence[float], *, orde
   place, tiles on the device are not copied); plan: the result of
   `plan_render` for `box`; inverted: {i: (tg_box, inverted_map)} as given to
   `plan_render`; weights: {i: blend_weights of the tile}; stride: zyx mesh
-  stride; order: 0 or 1, for the image (the weights are always sampled with
-  order 1).  Returns [z, y, x] of `out_dtype` (the tile dtype by default;
+  stride; order: 0 or 1, or with the switch SFM_SPLINE_ORDERS=1 2 to 5, for the
+  image (the weights are always sampled with order 1; orders 2 to 5 prefilter the `data_box` crops into a workspace of 8
+  bytes per crop voxel).  Returns [z, y, x] of `out_dtype` (the tile dtype by default;
   float32 is the only other choice), as NumPy or, with `device_output`, as a
   DeviceArray.
   """

@@ -19,7 +19,10 @@ images within 1.64e-6 of the image maximum).  Not pinned: bit parity with a
 real OpenCV build (which tap takes a table's rounding remainder).
 `ndimage_warp` (warp.py:189-335), the SciPy-only rendering path, is built as
 well and IS pinned: the reference function runs through the golden shim and
-the kernel reproduces its output bit for bit (tests/golden/ndimage_warp.npz).
+the kernel reproduces its output bit for bit (tests/golden/ndimage_warp.npz),
+for the spline orders 2 to 5 as well (ndimage_warp_spline.npz): those sample
+B-spline coefficients that a device prefilter computes in SciPy's operation
+order (sfm_spline_prefilter), and are opt-in (SFM_SPLINE_ORDERS=1).
 `warp_points` (warp.py:541-605) maps point sets through a coordinate map: one
 kernel, every point reads its four map nodes directly, pinned against the
 reference function through the golden shim (tests/golden/mapgeom.npz).
@@ -35,6 +38,7 @@ import torch
 
 from . import _abi
 from . import _dev
+from . import _spline
 from . import map_utils
 
 _INTER = {'nearest': 0, 'linear': 1, 'cubic': 2, 'lanczos': 3}
@@ -247,12 +251,18 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
   rounds of scipy.ndimage.map_coordinates per work box (dense coordinates by
   order-1 interpolation of the absolute map, then order-`order` sampling of the
   image), in double and in SciPy's operation order -- bit for bit the
-  reference's output (tests/golden/ndimage_warp.npz).  `work_size`, `overlap`
-  and `parallelism` only shape the reference's host loop and do not change the
-  result for orders 0 and 1; they are validated and otherwise unused.  Built:
-  order 0 and 1 with the default `map_coordinates`; higher spline orders,
-  custom samplers and uint64 label volumes raise NotImplementedError (use
-  `warp_subvolume` for label volumes).
+  reference's output (tests/golden/ndimage_warp.npz, ndimage_warp_spline.npz).
+  For orders 2 to 5 SciPy samples B-spline coefficients of the image: they are
+  computed once per call into a float64 workspace of 8 bytes per voxel
+  (`_spline.prefilter`; a request beyond the free-memory budget raises
+  MemoryError) and the same kernel samples them.  `work_size`, `overlap` and
+  `parallelism` only shape the reference's host loop and do not change the
+  result for any order (the reference prefilters the WHOLE image again for
+  every work box); they are validated and otherwise unused.  Built: orders 0
+  and 1, and with the switch SFM_SPLINE_ORDERS=1 (`_abi.set_option`) orders 2
+  to 5, with the default `map_coordinates`; without the switch orders above 1
+  raise NotImplementedError as they always did; custom samplers and uint64
+  label volumes raise it too (use `warp_subvolume` for label volumes).
   """
   del parallelism
   image = np.asarray(image)
@@ -268,8 +278,7 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
     raise NotImplementedError('ndimage_warp: custom map_coordinates callables run on the host only')
   if image.dtype == np.uint64:
     raise NotImplementedError('ndimage_warp: uint64 label volumes (use warp_subvolume)')
-  if order not in (0, 1):
-    raise NotImplementedError(f'ndimage_warp: interpolation order {order} (0 and 1 are built)')
+  _spline.check_order(order, 'ndimage_warp')
   if dim not in (2, 3):
     raise ValueError(f'ndimage_warp: {dim}-d data')
   if map_box is not None and image_box is None:
@@ -328,7 +337,14 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
   d.src_map = map_t.data_ptr()
   d.out = out_t.data_ptr()
   d.stream = _dev.stream_ptr()
-  _abi.check(_abi.load().sfm_ndimage_warp(C.byref(d)))
+  if order in _spline.ORDERS:
+    ishape = pad + tuple(image.shape)
+    coeffs, _ = _spline.prefilter(
+        [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev)
+    d.image = coeffs.data_ptr()
+    _abi.check(_abi.load().sfm_ndimage_warp_spline(C.byref(d)))
+  else:
+    _abi.check(_abi.load().sfm_ndimage_warp(C.byref(d)))
   warped = out_t.cpu().numpy()
   if image.dtype == np.uint16:
     warped = warped.view(np.uint16)
