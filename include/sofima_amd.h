@@ -1150,6 +1150,24 @@ int sfm_comm_allreduce_scalars(SfmComm* comm, float* inout, size_t count, int op
 int sfm_debug_fft1d(const void* in, void* out, int n, int n_in, int n_pencils,
                     int inverse, void* stream);
 
+/* Test hook (no reference counterpart; tests/test_gpu_mesh_edges.py): the integrator
+ * sfm_mesh_relax_chunk would run for `desc` under the switches in effect, from the same
+ * planner, without launching anything (no HIP call beyond the device's CU count; none of
+ * desc's pointers is dereferenced except `target`).  A persistent launch that times out
+ * falls back to what the other fields describe. */
+typedef struct SfmMeshPlanInfo {
+  int32_t persist_tile;         /* persistent single launch: tile edge 16 | 32, 0 not taken  */
+  int32_t persist_spec;         /* ... in its speculative form                                */
+  int32_t small;                /* mesh_small_kernel: every step of the chunk in one launch   */
+  int32_t tiled;                /* tiled in-plane step (integrate_shared2d_kernel)            */
+  int32_t fused;                /* ... as one launch per step (position update included)      */
+  int32_t packed;               /* ... with the narrow last tile column packed                */
+  int32_t march_t;              /* z-march kernel: threads per workgroup, 0 not taken         */
+  int32_t grid;                 /* workgroups of the per-node kernels                         */
+} SfmMeshPlanInfo;
+
+int sfm_debug_mesh_plan(const SfmMeshDesc* desc, SfmMeshPlanInfo* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -587,6 +587,11 @@ class SfmChunkStats(C.Structure):
   _fields_ = [('e_kin', C.c_float), ('v_max', C.c_float)]
 
 
+class SfmMeshPlanInfo(C.Structure):
+  _fields_ = [('persist_tile', i32), ('persist_spec', i32), ('small', i32), ('tiled', i32),
+              ('fused', i32), ('packed', i32), ('march_t', i32), ('grid', i32)]
+
+
 # name -> (restype, argtypes); mirrors include/sofima_amd.h one to one.
 SIGNATURES = {
     'sfm_version': (C.c_int, []),
@@ -656,6 +661,7 @@ SIGNATURES.update({
     'sfm_comm_destroy': (C.c_int, [C.c_void_p]),
     'sfm_debug_fft1d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p]),
+    'sfm_debug_mesh_plan': (C.c_int, [C.POINTER(SfmMeshDesc), C.POINTER(SfmMeshPlanInfo)]),
     'sfm_comm_halo_exchange': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]),

@@ -3339,7 +3339,9 @@ ChunkPlan plan_chunk(const SfmMeshDesc* d, const MeshParams* pp) {
   c.small = sfm::option_on("SFM_MESH_SMALL") && c.grid == 1 && d->num_iters > 0 && !c.dyn_prev &&
             p.force_kind != SFM_FORCE_EXTERNAL && !p.drift_cols && p.own_y0 <= 0 &&
             p.own_y1 >= p.Y;
-  c.tiled = c.tiles.tx && d->num_iters > 0;
+  // (a mesh of 160 .. 256 nodes fits both: mesh_small_kernel runs it and leaves the last
+  // step's update pending for finish_kernel, which the tiled step's finish mode would skip)
+  c.tiled = c.tiles.tx && d->num_iters > 0 && !c.small;
   // Native prev_fn on a tiled in-plane mesh: the target mesh is sampled from the
   // positions AFTER the position update, which the target kernel forms itself
   // from (x, v, a) on the overlap strips (sfm::AdvanceView) -- so the step is
@@ -3688,6 +3690,24 @@ int sfm_mesh_relax_chunk(const SfmMeshDesc* d, SfmFireState* fire,
   if (int rc = run.steps()) return rc;
   if (int rc = run.finish()) return rc;
   return read_back(run.st, &w.scal[run.cur], w.stats, p.fire, fire, stats);
+}
+
+// Test hook: what sfm_mesh_relax_chunk decides for `d` before its first launch.
+int sfm_debug_mesh_plan(const SfmMeshDesc* d, SfmMeshPlanInfo* info) {
+  MeshParams p;
+  if (int rc = build_params(d, &p)) return rc;
+  if (!info) return sfm::fail(SFM_ERR_INVALID, "info is NULL");
+  if (d->num_iters < 0) return sfm::fail(SFM_ERR_INVALID, "num_iters < 0");
+  const ChunkPlan c = plan_chunk(d, &p);
+  info->persist_tile = c.persist_tile;
+  info->persist_spec = c.persist_tile && c.persist_spec;
+  info->small = c.small;
+  info->tiled = c.tiled;
+  info->fused = c.fused;
+  info->packed = c.tiled && c.pack;
+  info->march_t = c.march.T;
+  info->grid = c.grid;
+  return SFM_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -86,6 +86,7 @@ def test_struct_layouts_match_header():
                      ('SfmMeshDesc', _abi.SfmMeshDesc),
                      ('SfmFireState', _abi.SfmFireState),
                      ('SfmChunkStats', _abi.SfmChunkStats),
+                     ('SfmMeshPlanInfo', _abi.SfmMeshPlanInfo),
                      ('SfmProfile', _abi.SfmProfile),
                      ('SfmMaskCountDesc', _abi.SfmMaskCountDesc),
                      ('SfmComposeDesc', _abi.SfmComposeDesc),

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import mesh_oracle
-from tests.util import cfg_from, load_cfgs
+from tests.util import cfg_from, load_cfgs, mesh_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -443,6 +443,15 @@ def test_integrator_paths_agree(gpu, variant):
   x0 = (rng.standard_normal(shape) * 0.5).astype(np.float32)
   pv = None if variant == 'no_prev' else prev
   run = lambda: mesh.relax_mesh(x0.copy(), None if pv is None else pv.copy(), cfg)
+  # the integrator each environment selects (sfm_debug_mesh_plan), not just a switch
+  plan = lambda: mesh_plan(x0, pv, cfg)
+  speculates = cfg.fire and not cfg.remove_drift
+  info = plan()
+  assert info.persist_tile in (16, 32) and bool(info.persist_spec) == speculates
+  info = _with_env({'SFM_MESH_PERSISTENT': '0'}, plan)
+  assert info.persist_tile == 0 and info.tiled and info.fused and not info.small
+  info = _with_env({'SFM_MESH_PERSISTENT': '0', 'SFM_MESH_TILED': '0'}, plan)
+  assert not (info.persist_tile or info.tiled or info.small or info.march_t)
   res = {
       'default': run(),
       'tiled': _with_env({'SFM_MESH_PERSISTENT': '0'}, run),
@@ -454,6 +463,8 @@ def test_integrator_paths_agree(gpu, variant):
     # the workgroups fit the chip (nw <= kMaxWg && nw <= CUs): 18 here
     assert 3 * -(-40 // 32) * -(-70 // 32) == 18 <= _device_cus()
     res['default32'] = _with_env({'SFM_MESH_TILE': '32'}, run)
+    info = _with_env({'SFM_MESH_TILE': '32'}, plan)
+    assert info.persist_tile == 32 and not info.persist_spec
   wx, we, wt = mesh_oracle.relax_mesh(x0.copy(), None if pv is None else pv.copy(),
                                       cfg)
   scale = np.abs(wx).max()
@@ -686,7 +697,7 @@ def test_speculative_hand_off_fuzz(gpu):
   print(f'hand-off fuzz: {cases} cases, {uphill_cases} with uphill events, 0 mismatches')
 
 
-@pytest.mark.parametrize('case', ['tile2d', 'tile3d', 'vol3d', 'plane_vv'])
+@pytest.mark.parametrize('case', ['tile2d', 'tile3d', 'vol3d', 'vol3d_global', 'plane_vv'])
 def test_small_mesh_single_launch_is_bit_identical(gpu, case):
   """mesh_small_kernel (meshes of at most one workgroup's worth of nodes: all
   steps of a chunk in one launch) == the kernel-per-phase path, bit for bit."""
@@ -711,8 +722,10 @@ def test_small_mesh_single_launch_is_bit_identical(gpu, case):
     np.testing.assert_array_equal(a, b)
     assert np.isfinite(a).all() and np.abs(a).max() > 100
     return
-  if case == 'vol3d':
-    shape = (3, 1, 6, 6, 6)
+  if case in ('vol3d', 'vol3d_global'):
+    # 5-D: drift means per x column (the reference's axes quirk), which mesh_small_kernel
+    # does not take -- both runs are the kernel-per-phase path; 4-D: the global means
+    shape = (3, 1, 6, 6, 6) if case == 'vol3d' else (3, 6, 6, 6)
     stride = (40.0, 40.0, 40.0)
     kw = dict(mesh_force=mesh.elastic_mesh_3d)
     cfg_kw = dict(remove_drift=True, prefer_orig_order=False)
@@ -731,6 +744,12 @@ def test_small_mesh_single_launch_is_bit_identical(gpu, case):
                                **cfg_kw)
   x0 = np.zeros(shape, np.float32)
   vv = lambda: mesh.velocity_verlet(x0, np.zeros_like(x0), prev, cfg, cfg.start_cap, **kw)
+  plan = lambda: mesh_plan(x0, prev, cfg, kw.get('mesh_force'))
+  info = _with_env({'SFM_MESH_SMALL': '1', 'SFM_MESH_PERSISTENT': '0'}, plan)
+  assert bool(info.small) == (case != 'vol3d')
+  assert not (info.persist_tile or info.tiled or info.march_t)
+  info = _with_env({'SFM_MESH_SMALL': '0', 'SFM_MESH_PERSISTENT': '0'}, plan)
+  assert not (info.small or info.persist_tile or info.tiled or info.march_t) and info.grid == 1
   a = _with_env({'SFM_MESH_SMALL': '1', 'SFM_MESH_PERSISTENT': '0'}, vv)
   b = _with_env({'SFM_MESH_SMALL': '0', 'SFM_MESH_PERSISTENT': '0'}, vv)
   for u, w in zip(a[:3], b[:3]):

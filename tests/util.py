@@ -60,6 +60,24 @@ def load_cfgs(npz):
   return json.loads(str(npz['cfgs']))
 
 
+def mesh_plan(x, prev, config, mesh_force=None):
+  """Which integrator sfm_mesh_relax_chunk would run for this velocity_verlet call
+  under the switches in effect (sfm_debug_mesh_plan): an _abi.SfmMeshPlanInfo.  Needs
+  a GPU (the planner compares with the device's CU count)."""
+  import ctypes as C
+  import torch
+  from sofima_amd import _abi, _dev, mesh
+  spec = mesh._resolve_force(mesh_force or mesh.inplane_force)
+  dev = _dev.device()
+  x_t = _dev.as_device_f32(x, dev, copy=False)
+  prev_t = None if prev is None else _dev.as_device_f32(prev, dev, copy=False)
+  ws = torch.empty(1, dtype=torch.uint8, device=dev)
+  d = mesh._chunk_desc(x_t, x_t, x_t, prev_t, config, spec, ws)   # nothing is dereferenced
+  info = _abi.SfmMeshPlanInfo()
+  _abi.check(_abi.load().sfm_debug_mesh_plan(C.byref(d), C.byref(info)))
+  return info
+
+
 def em_texture(rng, shape, sigma=2.0):
   """uint8 EM-like texture (low-pass noise stretched to 0..255)."""
   from scipy import ndimage
