@@ -44,7 +44,8 @@ extern "C" {
                                    sfm_prev_state, sfm_mask_irregular_f64,
                                    sfm_render_tiles3d, and sfm_spline_prefilter,
                                    sfm_ndimage_warp_spline and
-                                   sfm_render_tiles3d_spline */
+                                   sfm_render_tiles3d_spline, and
+                                   sfm_ndimage_warp_mode and sfm_affine_warp */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -768,6 +769,58 @@ int sfm_ndimage_warp_spline(const SfmNdWarpDesc* desc);
  * data_size, back to back in table order (sfm_spline_prefilter with one item
  * per entry); `image` of an entry is not read. */
 int sfm_render_tiles3d_spline(const SfmRenderTilesDesc* desc, const double* coeffs);
+
+/* ------------------------------------------------------------------------
+ * SciPy's boundary modes and fill value for the samplers (sfm_ndsample.h), as
+ * scipy.ndimage.map_coordinates(mode=, cval=) applies them: restated from
+ * SciPy's behaviour in tests/ndwarp_modes_ref.py, which a CPU test pins to SciPy
+ * bit for bit.  Orders 0 and 1 take every mode; orders 2 .. 5 take CONSTANT,
+ * MIRROR and WRAP, whose B-spline coefficients are those of
+ * sfm_spline_prefilter (the others need another prefilter and are rejected).
+ * An integer image takes cval through the conversion of a sampled value and
+ * needs a finite one.  A NaN coordinate, or one of magnitude 2^31 and above,
+ * gives cval under every mode (SciPy casts it to an integer there, which is
+ * undefined, except under CONSTANT); no coordinate reads outside the array.
+ * ---------------------------------------------------------------------- */
+#define SFM_MODE_CONSTANT 0        /* outside [0, len - 1]: cval                 */
+#define SFM_MODE_GRID_CONSTANT 1   /* taps outside the array read cval           */
+#define SFM_MODE_NEAREST 2         /* taps clamped to the edge sample            */
+#define SFM_MODE_MIRROR 3          /* period 2 len - 2                           */
+#define SFM_MODE_REFLECT 4         /* period 2 len ("grid-mirror")               */
+#define SFM_MODE_WRAP 5            /* period len - 1                             */
+#define SFM_MODE_GRID_WRAP 6       /* period len                                 */
+
+/* sfm_ndimage_warp / sfm_ndimage_warp_spline (by desc->order: 2 .. 5 read
+ * coefficients from desc->image) with a boundary mode on BOTH steps, as the
+ * reference passes one map_coordinates callable to both (warp.py:308-314):
+ * outside the node grid the dense coordinate is cval, in source voxels, or the
+ * folded node value, and the image sample follows the same rule. */
+int sfm_ndimage_warp_mode(const SfmNdWarpDesc* desc, int32_t mode, double cval);
+
+/* scipy.ndimage.affine_transform(image, matrix, offset, order=, mode=, cval=)
+ * with a [dim, dim] matrix, output of the input's shape, as ONE kernel and
+ * without a coordinate map: per output voxel o the source coordinate
+ *   c[h] = ((0 + o[0] M[h][0]) + o[1] M[h][1] [+ o[2] M[h][2]]) + offset[h]
+ * in double and in this order (SciPy's, offset last), then the samplers. */
+typedef struct SfmAffineWarpDesc {
+  int32_t ndim;                 /* 2 or 3                                      */
+  int32_t dtype;                /* SFM_DTYPE_U8 | U16 | F32 of image and out   */
+  int32_t order;                /* 0 .. 5; 2 .. 5: image holds the float64
+                                   B-spline coefficients (sfm_spline_prefilter),
+                                   dtype is the type of out alone              */
+  int32_t mode;                 /* SFM_MODE_*                                  */
+  int32_t shape[3];             /* z, y, x of image and out; 2-D: shape[0] = 1 */
+  int32_t reserved;             /* 0                                           */
+  double matrix[9];             /* row-major [3][3] over the axes z, y, x; 2-D
+                                   reads rows and columns 1 and 2              */
+  double offset[3];             /* z, y, x                                     */
+  double cval;
+  const void* image;            /* device [z, y, x]                            */
+  void* out;                    /* device [z, y, x]                            */
+  void* stream;
+} SfmAffineWarpDesc;
+
+int sfm_affine_warp(const SfmAffineWarpDesc* desc);
 
 /* ------------------------------------------------------------------------
  * Map geometry: the one-pass helpers that the reference's renderers call

@@ -22,6 +22,9 @@ DTYPE_U16 = 2
 DTYPE_I32 = 3
 WARP_NEAREST = 0
 WARP_TABLE = 1
+# SFM_MODE_*: SciPy's boundary modes by name ('grid-mirror' is 'reflect')
+MODES = {'constant': 0, 'grid-constant': 1, 'nearest': 2, 'mirror': 3, 'reflect': 4,
+         'grid-mirror': 4, 'wrap': 5, 'grid-wrap': 6}
 XCORR_AUTO = 0
 XCORR_DIRECT = 1
 XCORR_MFMA_I8 = 2
@@ -291,6 +294,23 @@ class SfmNdWarpDesc(C.Structure):
       ('offset', C.c_double * 3),
       ('image', C.c_void_p),
       ('src_map', C.c_void_p),
+      ('out', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
+class SfmAffineWarpDesc(C.Structure):
+  _fields_ = [
+      ('ndim', i32),
+      ('dtype', i32),
+      ('order', i32),
+      ('mode', i32),
+      ('shape', i32 * 3),
+      ('reserved', i32),
+      ('matrix', C.c_double * 9),
+      ('offset', C.c_double * 3),
+      ('cval', C.c_double),
+      ('image', C.c_void_p),
       ('out', C.c_void_p),
       ('stream', C.c_void_p),
   ]
@@ -630,6 +650,8 @@ SIGNATURES = {
     'sfm_spline_prefilter': (C.c_int, [C.POINTER(SfmSplinePrefilterDesc)]),
     'sfm_ndimage_warp_spline': (C.c_int, [C.POINTER(SfmNdWarpDesc)]),
     'sfm_render_tiles3d_spline': (C.c_int, [C.POINTER(SfmRenderTilesDesc), C.c_void_p]),
+    'sfm_ndimage_warp_mode': (C.c_int, [C.POINTER(SfmNdWarpDesc), i32, C.c_double]),
+    'sfm_affine_warp': (C.c_int, [C.POINTER(SfmAffineWarpDesc)]),
     'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),
     'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
     'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),

@@ -1,8 +1,13 @@
-// scipy.ndimage.map_coordinates on the device, orders 0 to 5, mode "constant",
-// cval 0: the samplers shared by ndimage_warp_kernel and render_tiles_kernel
-// (sfm_warp.hip).  Orders 0 and 1 read the image, orders 2 to 5 its float64
-// B-spline coefficients (sfm_spline.hip).  Double arithmetic in SciPy's operation
-// order; the units that include this are built with -ffp-contract=off.
+// scipy.ndimage.map_coordinates on the device, orders 0 to 5: the samplers shared
+// by the kernels of sfm_warp.hip.  Orders 0 and 1 read the image, orders 2 to 5
+// its float64 B-spline coefficients (sfm_spline.hip).  Double arithmetic in SciPy's
+// operation order; the units that include this are built with -ffp-contract=off.
+//
+// Every sampler has two instantiations.  MODES = false is mode "constant" with
+// cval 0 and nothing else (ndimage_warp_kernel, render_tiles_kernel).  MODES =
+// true takes a Boundary, SciPy's boundary mode and fill value, at run time (the
+// mode is uniform over a launch): fold_coordinate and fold_tap below, restated
+// from SciPy's behaviour in tests/ndwarp_modes_ref.py.
 //
 // `a` is anything indexable by a linear element offset whose elements widen to
 // double: a pointer, or a view such as ShiftedMap below.  `shape` holds 3
@@ -18,13 +23,122 @@
 
 namespace sfm {
 
+// SciPy's boundary modes (SFM_MODE_* of the public header) and the fill value.
+enum : int {
+  kModeConstant = 0, kModeGridConstant = 1, kModeNearest = 2, kModeMirror = 3,
+  kModeReflect = 4, kModeWrap = 5, kModeGridWrap = 6, kModeCount = 7
+};
+struct Boundary {
+  int mode = kModeConstant;
+  double cval = 0.0;
+};
+
+// The coordinate `c` on an axis of length `len`, folded by the mode.  false: the
+// sample is cval as a whole -- "constant" outside [0, len - 1] (NaN included), and
+// under every other mode a NaN or a magnitude of 2^31 and above, which SciPy casts
+// to an integer (undefined).  "grid-constant" and "nearest" leave the coordinate
+// where it is and treat the taps; the others fold it with SciPy's periods: 2 len - 2
+// "mirror", 2 len "reflect" (a coordinate within 1e-15 below 0 lands on 1e-15 - 1),
+// len - 1 "wrap", len "grid-wrap"; SciPy's (npy_intp) casts are trunc().
+__device__ __forceinline__ bool fold_coordinate(int mode, int len, double& c) {
+  if (mode == kModeConstant) return c >= 0.0 && c <= static_cast<double>(len - 1);
+  if (!(fabs(c) < 2147483648.0)) return false;
+  if (mode == kModeGridConstant || mode == kModeNearest) return true;
+  const bool lo = c < 0.0;
+  if (!lo && !(c > static_cast<double>(len - 1))) return true;
+  if (len <= 1) {
+    c = 0.0;
+    return true;
+  }
+  const double n = static_cast<double>(len);
+  switch (mode) {
+    case kModeMirror: {
+      const double sz2 = 2.0 * n - 2.0;
+      if (lo) {
+        const double v = sz2 * trunc(-c / sz2) + c;
+        c = v <= 1.0 - n ? v + sz2 : -v;
+      } else {
+        const double v = c - sz2 * trunc(c / sz2);
+        c = v >= n ? sz2 - v : v;
+      }
+      break;
+    }
+    case kModeReflect: {
+      const double sz2 = 2.0 * n;
+      if (lo) {
+        double v = c;
+        if (v < -sz2) v = sz2 * trunc(-v / sz2) + v;
+        c = v < -n ? v + sz2 : (v > -1e-15 ? 1e-15 : -v) - 1.0;
+      } else {
+        const double v = c - sz2 * trunc(c / sz2);
+        c = v >= n ? sz2 - v - 1.0 : v;
+      }
+      break;
+    }
+    case kModeWrap: {
+      const double sz = n - 1.0;
+      c = lo ? c + sz * (trunc(-c / sz) + 1.0) : c - sz * trunc(c / sz);
+      break;
+    }
+    default: {  // kModeGridWrap
+      if (lo) {
+        c = c + n * (trunc((-1.0 - c) / n) + 1.0);
+      } else {
+        const double v = c - n * trunc((c + 1.0) / n);
+        c = v < 0.0 ? v + n : v;
+      }
+      break;
+    }
+  }
+  return true;
+}
+
+// The tap index `i` folded into [0, len - 1], for every i: "nearest" clamps,
+// "reflect" repeats the edge sample, "grid-wrap" has period len; "constant",
+// "mirror" and "wrap" mirror without repeating the edge sample ("wrap" folds only
+// its coordinate with period len - 1).  Under "grid-constant" a tap outside the
+// array is not read: `fill` is set and the tap's value is cval.
+__device__ __forceinline__ long long fold_tap(int mode, int len, long long i, bool& fill) {
+  fill = false;
+  if (i >= 0 && i < len) return i;
+  if (mode == kModeGridConstant) {
+    fill = true;
+    return 0;
+  }
+  if (len <= 1) return 0;
+  switch (mode) {
+    case kModeNearest:
+      return i < 0 ? 0 : len - 1;
+    case kModeReflect: {
+      const long long p = 2LL * len;
+      long long j = i % p;
+      j = j < 0 ? j + p : j;
+      return j >= len ? p - 1 - j : j;
+    }
+    case kModeGridWrap: {
+      const long long j = i % len;
+      return j < 0 ? j + len : j;
+    }
+    default: {
+      const long long p = 2LL * len - 2;
+      long long j = i < 0 ? -i : i;
+      j = j % p;
+      return j >= len ? p - j : j;
+    }
+  }
+}
+
 // scipy NI_GeometricTransform, order 1, mode "constant", cval 0: outside
 // [0, len - 1] on any axis, NaN included -> 0; the tap beyond the last sample
 // (coordinate exactly len - 1) carries weight 0 and is read mirrored, from
 // len - 2, as SciPy's edge mapping does: 0 x inf and 0 x NaN there are NaN.
-template <int DIM, typename A>
+//
+// MODES: the coordinate is folded first, every tap is folded after it, a tap that
+// "grid-constant" finds outside the array is cval.
+template <int DIM, bool MODES = false, typename A>
 __device__ __forceinline__ double linear_sample(const A a, const int* shape, const double* c,
-                                                const long long* pitch = nullptr) {
+                                                const long long* pitch = nullptr,
+                                                const Boundary b = Boundary()) {
   long long base[DIM];
   double w[DIM][2];
   long long dense = 1;
@@ -37,9 +151,14 @@ __device__ __forceinline__ double linear_sample(const A a, const int* shape, con
 #pragma unroll
   for (int d = 0; d < DIM; ++d) {
     const int len = shape[3 - DIM + d];
-    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
-    const double fl = floor(c[d]);
-    const double t = c[d] - fl;
+    double cc = c[d];
+    if constexpr (MODES) {
+      if (!fold_coordinate(b.mode, len, cc)) return b.cval;
+    } else {
+      if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
+    }
+    const double fl = floor(cc);
+    const double t = cc - fl;
     w[d][0] = 1.0 - t;
     w[d][1] = 1.0 - w[d][0];
     base[d] = static_cast<long long>(fl);
@@ -48,15 +167,22 @@ __device__ __forceinline__ double linear_sample(const A a, const int* shape, con
 #pragma unroll
   for (int tap = 0; tap < (1 << DIM); ++tap) {
     long long idx = 0;
+    bool fill = false;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) {
       const int bit = (tap >> (DIM - 1 - d)) & 1;
       const int len = shape[3 - DIM + d];
       long long i = base[d] + bit;
-      if (i > len - 1) i = len > 1 ? len - 2 : 0;
+      if constexpr (MODES) {
+        bool f;
+        i = fold_tap(b.mode, len, i, f);
+        fill = fill || f;
+      } else {
+        if (i > len - 1) i = len > 1 ? len - 2 : 0;
+      }
       idx += i * step[d];
     }
-    double coeff = static_cast<double>(a[idx]);
+    double coeff = fill ? b.cval : static_cast<double>(a[idx]);
 #pragma unroll
     for (int d = 0; d < DIM; ++d) coeff = coeff * w[d][(tap >> (DIM - 1 - d)) & 1];
     acc = acc + coeff;
@@ -119,9 +245,13 @@ __device__ __forceinline__ void spline_weights<5>(double x, double* w) {
 // orders, floor(c + 0.5) for even ones; ORDER + 1 taps per axis from
 // base - ORDER / 2, indices outside the array mirrored without repeating the edge
 // sample; coefficient x weights in axis order, taps added in row-major order.
-template <int DIM, int ORDER, typename A>
+//
+// MODES: "constant" with a fill value, "mirror" and "wrap", the modes whose
+// coefficients are these; only the coordinate is folded, the taps mirror as above.
+template <int DIM, int ORDER, bool MODES = false, typename A>
 __device__ __forceinline__ double spline_sample(const A a, const int* shape, const double* c,
-                                                const long long* pitch = nullptr) {
+                                                const long long* pitch = nullptr,
+                                                const Boundary b = Boundary()) {
   constexpr int K = ORDER + 1;
   double w[DIM][K];
   long long off[DIM][K];
@@ -135,9 +265,14 @@ __device__ __forceinline__ double spline_sample(const A a, const int* shape, con
 #pragma unroll
   for (int d = 0; d < DIM; ++d) {
     const int len = shape[3 - DIM + d];
-    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
-    const double base = (ORDER & 1) ? floor(c[d]) : floor(c[d] + 0.5);
-    spline_weights<ORDER>(c[d] - base, w[d]);
+    double cc = c[d];
+    if constexpr (MODES) {
+      if (!fold_coordinate(b.mode, len, cc)) return b.cval;
+    } else {
+      if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
+    }
+    const double base = (ORDER & 1) ? floor(cc) : floor(cc + 0.5);
+    spline_weights<ORDER>(cc - base, w[d]);
     const long long start = static_cast<long long>(base) - ORDER / 2;
     const long long period = 2LL * len - 2;
 #pragma unroll
@@ -185,20 +320,33 @@ __device__ __forceinline__ double spline_sample(const A a, const int* shape, con
   return acc;
 }
 
-template <int DIM, typename A>
+template <int DIM, bool MODES = false, typename A>
 __device__ __forceinline__ double nearest_sample(const A a, const int* shape, const double* c,
-                                                 const long long* pitch = nullptr) {
+                                                 const long long* pitch = nullptr,
+                                                 const Boundary b = Boundary()) {
   long long idx = 0, dense = 1;
+  bool fill = false;
 #pragma unroll
   for (int d = DIM - 1; d >= 0; --d) {
     const int len = shape[3 - DIM + d];
-    if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
-    long long i = static_cast<long long>(floor(c[d] + 0.5));
-    i = i > len - 1 ? len - 1 : i;
+    double cc = c[d];
+    if constexpr (MODES) {
+      if (!fold_coordinate(b.mode, len, cc)) return b.cval;
+    } else {
+      if (!(c[d] >= 0.0 && c[d] <= static_cast<double>(len - 1))) return 0.0;
+    }
+    long long i = static_cast<long long>(floor(cc + 0.5));
+    if constexpr (MODES) {
+      bool f;
+      i = fold_tap(b.mode, len, i, f);
+      fill = fill || f;
+    } else {
+      i = i > len - 1 ? len - 1 : i;
+    }
     idx += i * (pitch ? pitch[3 - DIM + d] : dense);
     dense *= len;
   }
-  return static_cast<double>(a[idx]);
+  return fill ? b.cval : static_cast<double>(a[idx]);
 }
 
 // double -> output type like NI's CASE_INTERP_OUT_*: unsigned types add 0.5 to

@@ -234,13 +234,69 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
   static_cast<T*>(a.out)[i] = sfm::nd_convert<T>(v, vmax);
 }
 
+// The same with SciPy's boundary mode and fill value on BOTH steps, as the
+// reference hands one map_coordinates callable to both (warp.py:308-314): outside
+// the node grid the dense coordinate is cval (in source voxels) or the folded
+// node value, and the image sample follows the same rule; an integer image takes
+// cval through nd_convert like a sampled value.
+template <int DIM, typename T, int ORDER = 0>
+__global__ void __launch_bounds__(kBlock) ndimage_warp_mode_kernel(NdWarpArgs a, sfm::Boundary b) {
+  const long long n = (long long)a.oshape[0] * a.oshape[1] * a.oshape[2];
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  int o[3];
+  o[2] = static_cast<int>(i % a.oshape[2]);
+  o[1] = static_cast<int>((i / a.oshape[2]) % a.oshape[1]);
+  o[0] = static_cast<int>(i / ((long long)a.oshape[2] * a.oshape[1]));
+  double pos[DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    const int ax = 3 - DIM + d;
+    pos[d] = (static_cast<double>(o[ax]) - a.offset[ax]) / a.stride[ax];
+  }
+  const long long nodes = (long long)a.mshape[0] * a.mshape[1] * a.mshape[2];
+  double dense[DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d)
+    dense[d] = sfm::linear_sample<DIM, true>(a.map + (long long)(DIM - 1 - d) * nodes, a.mshape,
+                                             pos, nullptr, b);
+  double v;
+  if constexpr (ORDER >= 2) {
+    v = sfm::spline_sample<DIM, ORDER, true>(static_cast<const double*>(a.image), a.ishape,
+                                             dense, nullptr, b);
+  } else {
+    const T* img = static_cast<const T*>(a.image);
+    v = a.order == 0 ? sfm::nearest_sample<DIM, true>(img, a.ishape, dense, nullptr, b)
+                     : sfm::linear_sample<DIM, true>(img, a.ishape, dense, nullptr, b);
+  }
+  constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
+  static_cast<T*>(a.out)[i] = sfm::nd_convert<T>(v, vmax);
+}
+
+// What the samplers take: a mode of the list; orders 2 .. 5 only the modes whose
+// coefficients sfm_spline_prefilter computes; a finite fill value for integers
+// (the conversion of NaN or an infinity to an integer is undefined).
+int check_boundary(const char* what, int mode, double cval, int order, int dtype) {
+  if (mode < 0 || mode >= sfm::kModeCount)
+    return sfm::fail(SFM_ERR_INVALID, "%s: boundary mode %d", what, mode);
+  if (order >= 2 && mode != sfm::kModeConstant && mode != sfm::kModeMirror &&
+      mode != sfm::kModeWrap)
+    return sfm::fail(SFM_ERR_INVALID,
+                     "%s: boundary mode %d at order %d (constant, mirror and wrap are built)",
+                     what, mode, order);
+  if (dtype != SFM_DTYPE_F32 && !std::isfinite(cval))
+    return sfm::fail(SFM_ERR_INVALID, "%s: non-finite cval for an integer image", what);
+  return SFM_OK;
+}
+
 }  // namespace
 
 namespace {
 
-// the checks and the launch of sfm_ndimage_warp (orders 0, 1 on the image) and
-// sfm_ndimage_warp_spline (orders 2 .. 5 on coefficients)
-int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline) {
+// the checks and the launch of sfm_ndimage_warp (orders 0, 1 on the image),
+// sfm_ndimage_warp_spline (orders 2 .. 5 on coefficients) and, with a Boundary,
+// sfm_ndimage_warp_mode (either)
+int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline, const sfm::Boundary* bnd = nullptr) {
   if (!d || !d->image || !d->src_map || !d->out)
     return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: NULL argument");
   if (d->ndim != 2 && d->ndim != 3) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: ndim %d", d->ndim);
@@ -277,7 +333,11 @@ int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline) {
   const dim3 g(static_cast<unsigned>(grid)), b(kBlock);
 #define SFM_NDW_ORDER(T, ORDER)                                                    \
   do {                                                                             \
-    if (d->ndim == 2)                                                              \
+    if (bnd && d->ndim == 2)                                                       \
+      hipLaunchKernelGGL((ndimage_warp_mode_kernel<2, T, ORDER>), g, b, 0, st, a, *bnd); \
+    else if (bnd)                                                                  \
+      hipLaunchKernelGGL((ndimage_warp_mode_kernel<3, T, ORDER>), g, b, 0, st, a, *bnd); \
+    else if (d->ndim == 2)                                                         \
       hipLaunchKernelGGL((ndimage_warp_kernel<2, T, ORDER>), g, b, 0, st, a);      \
     else                                                                           \
       hipLaunchKernelGGL((ndimage_warp_kernel<3, T, ORDER>), g, b, 0, st, a);      \
@@ -310,6 +370,125 @@ extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) { return ndimage_warp_la
 
 extern "C" int sfm_ndimage_warp_spline(const SfmNdWarpDesc* d) {
   return ndimage_warp_launch(d, true);
+}
+
+extern "C" int sfm_ndimage_warp_mode(const SfmNdWarpDesc* d, int32_t mode, double cval) {
+  if (!d) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_mode: NULL argument");
+  if (d->order < 0 || d->order > 5)
+    return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_mode: interpolation order %d (0 .. 5)",
+                     d->order);
+  if (int rc = check_boundary("ndimage_warp_mode", mode, cval, d->order, d->dtype)) return rc;
+  sfm::Boundary b;
+  b.mode = mode;
+  b.cval = cval;
+  return ndimage_warp_launch(d, d->order >= 2, &b);
+}
+
+// ---------------------------------------------------------------------------
+// scipy.ndimage.affine_transform with a [dim, dim] matrix: the source coordinate
+// of an output voxel is a matrix product and an offset, formed in double from
+// kernel arguments (scalar registers) -- products added in axis order onto 0,
+// the offset last, which is SciPy's rounding -- and handed to the samplers.  No
+// coordinate map exists.  One thread per output voxel, a wave per 64 contiguous
+// voxels, as in ndimage_warp_kernel.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct AffineArgs {
+  const void* image;
+  void* out;
+  int order;
+  int shape[3];
+  double m[3][3], off[3];
+  sfm::Boundary b;
+};
+
+template <int DIM, typename T, int ORDER = 0>
+__global__ void __launch_bounds__(kBlock) affine_warp_kernel(AffineArgs a) {
+  const long long n = (long long)a.shape[0] * a.shape[1] * a.shape[2];
+  const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (i >= n) return;
+  int o[3];
+  o[2] = static_cast<int>(i % a.shape[2]);
+  o[1] = static_cast<int>((i / a.shape[2]) % a.shape[1]);
+  o[0] = static_cast<int>(i / ((long long)a.shape[2] * a.shape[1]));
+  double c[DIM];
+#pragma unroll
+  for (int h = 0; h < DIM; ++h) {
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k)
+      acc = acc + static_cast<double>(o[3 - DIM + k]) * a.m[3 - DIM + h][3 - DIM + k];
+    c[h] = acc + a.off[3 - DIM + h];
+  }
+  double v;
+  if constexpr (ORDER >= 2) {
+    v = sfm::spline_sample<DIM, ORDER, true>(static_cast<const double*>(a.image), a.shape, c,
+                                             nullptr, a.b);
+  } else {
+    const T* img = static_cast<const T*>(a.image);
+    v = a.order == 0 ? sfm::nearest_sample<DIM, true>(img, a.shape, c, nullptr, a.b)
+                     : sfm::linear_sample<DIM, true>(img, a.shape, c, nullptr, a.b);
+  }
+  constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
+  static_cast<T*>(a.out)[i] = sfm::nd_convert<T>(v, vmax);
+}
+
+}  // namespace
+
+extern "C" int sfm_affine_warp(const SfmAffineWarpDesc* d) {
+  if (!d || !d->image || !d->out) return sfm::fail(SFM_ERR_INVALID, "affine_warp: NULL argument");
+  if (d->ndim != 2 && d->ndim != 3) return sfm::fail(SFM_ERR_INVALID, "affine_warp: ndim %d", d->ndim);
+  if (d->order < 0 || d->order > 5)
+    return sfm::fail(SFM_ERR_INVALID, "affine_warp: interpolation order %d (0 .. 5)", d->order);
+  if (int rc = check_boundary("affine_warp", d->mode, d->cval, d->order, d->dtype)) return rc;
+  AffineArgs a;
+  a.image = d->image;
+  a.out = d->out;
+  a.order = d->order;
+  a.b.mode = d->mode;
+  a.b.cval = d->cval;
+  long long n = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (d->shape[k] < 1) return sfm::fail(SFM_ERR_INVALID, "affine_warp: bad shape");
+    if (d->ndim == 2 && k == 0 && d->shape[0] != 1)
+      return sfm::fail(SFM_ERR_INVALID, "affine_warp: 2-d arrays have shape[0] = 1");
+    a.shape[k] = d->shape[k];
+    a.off[k] = d->offset[k];
+    for (int j = 0; j < 3; ++j) a.m[k][j] = d->matrix[3 * k + j];
+    n *= d->shape[k];
+  }
+  const long long grid = (n + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffffLL) return sfm::fail(SFM_ERR_INVALID, "affine_warp: too large");
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  const dim3 g(static_cast<unsigned>(grid)), b(kBlock);
+#define SFM_AFF_ORDER(T, ORDER)                                                    \
+  do {                                                                             \
+    if (d->ndim == 2)                                                              \
+      hipLaunchKernelGGL((affine_warp_kernel<2, T, ORDER>), g, b, 0, st, a);       \
+    else                                                                           \
+      hipLaunchKernelGGL((affine_warp_kernel<3, T, ORDER>), g, b, 0, st, a);       \
+  } while (0)
+#define SFM_AFF(T)                                                                 \
+  do {                                                                             \
+    switch (d->order) {                                                            \
+      case 2: SFM_AFF_ORDER(T, 2); break;                                          \
+      case 3: SFM_AFF_ORDER(T, 3); break;                                          \
+      case 4: SFM_AFF_ORDER(T, 4); break;                                          \
+      case 5: SFM_AFF_ORDER(T, 5); break;                                          \
+      default: SFM_AFF_ORDER(T, 0); break;                                         \
+    }                                                                              \
+  } while (0)
+  switch (d->dtype) {
+    case SFM_DTYPE_U8: SFM_AFF(unsigned char); break;
+    case SFM_DTYPE_U16: SFM_AFF(unsigned short); break;
+    case SFM_DTYPE_F32: SFM_AFF(float); break;
+    default: return sfm::fail(SFM_ERR_INVALID, "affine_warp: dtype %d", d->dtype);
+  }
+#undef SFM_AFF
+#undef SFM_AFF_ORDER
+  SFM_LAUNCH_CHECK();
+  return SFM_OK;
 }
 
 // ---------------------------------------------------------------------------

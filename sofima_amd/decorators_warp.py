@@ -1,0 +1,96 @@
+"""The array-level warps of the reference's decorators/warp.py on MI355X: the two
+functions that sit between coarse (affine) alignment and the elastic pipeline.
+
+`warp_affine` is `_warp_affine` (decorators/warp.py:36-116) and `warp_coord_map`
+is `_warp_coord_map` (:221-243); the private names are kept as aliases.  Both take
+and return NumPy arrays in xyz axis order.  The TensorStore decorator classes
+around them (WarpAffine, WarpCoordMap) are volume I/O and are not built.
+
+Pinned: the reference's own functions run through the golden shim
+(tests/golden/warp_decorators.npz) and these reproduce their output bit for bit
+(tests/test_gpu_decorators_warp.py).
+"""
+from __future__ import annotations
+
+import functools
+import types
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import map_utils
+from . import warp
+
+
+def warp_affine(img_xyz: np.ndarray, matrix_xyz: np.ndarray, order: int = 1,
+                implementation: str = 'scipy', **warp_args) -> np.ndarray:
+  """Warp affine in 2D/3D (decorators/warp.py:36-116).
+
+  img_xyz: 2-D or 3-D uint8 / uint16 / float32 image; matrix_xyz: the forward
+  transform, (dim, dim + 1) or its homogeneous form (dim + 1, dim + 1).
+  implementation 'scipy': the matrix is inverted on the host (np.linalg.inv, as
+  the reference does) and `warp.affine_transform` resamples in one fused kernel.
+  'sofima' (3-D only): `map_utils.make_affine_map` at stride 1, then
+  `warp.ndimage_warp` of the transposed image, both on the device; `warp_args`
+  go to `ndimage_warp`.  'opencv' needs cv2, which is neither available nor
+  pinned here (like `warp.warp_subvolume`'s resampling), and raises
+  NotImplementedError.
+  """
+  img_xyz = np.asarray(img_xyz)
+  matrix_xyz = np.asarray(matrix_xyz)
+  dim = img_xyz.ndim
+  if dim not in (2, 3):
+    raise ValueError(f'2 or 3 image dimensions are required, but got {dim}.')
+  if matrix_xyz.ndim != 2:
+    raise ValueError(f'2 matrix dimensions are required, but got {matrix_xyz.ndim}.')
+  rows, cols = matrix_xyz.shape
+  if cols != dim + 1:
+    raise ValueError(f'{dim + 1} matrix cols are required, but got {cols}.')
+  if rows not in (dim, dim + 1):
+    raise ValueError(f'{dim} or {dim + 1} matrix rows are required, but got {rows}.')
+  homogeneous = np.eye(dim + 1)
+  homogeneous[:rows] = matrix_xyz
+
+  if implementation == 'opencv':
+    if dim != 2:
+      raise RuntimeError('Only 2D images are supported with `implementation=opencv`.')
+    raise NotImplementedError(
+        'warp_affine: implementation=opencv needs cv2, which is not available here')
+  if implementation == 'scipy':
+    return warp.affine_transform(img_xyz, np.linalg.inv(homogeneous), order=order)
+  if implementation != 'sofima':
+    raise ValueError(
+        f'implementation must be `opencv`, `scipy`, or `sofima`, but got `{implementation}.')
+  if dim != 3:
+    raise RuntimeError('Only 3D images are supported with `implementation=sofima`.')
+  box = types.SimpleNamespace(start=np.zeros(3, np.int64), size=np.array(img_xyz.shape, np.int64))
+  coord_map = map_utils.make_affine_map(np.linalg.inv(homogeneous)[:3, :], box, [1, 1, 1])
+  warp_args.setdefault('work_size', img_xyz.shape)
+  return warp.ndimage_warp(img_xyz.T, np.asarray(coord_map), stride=[1, 1, 1], order=order,
+                           overlap=[0, 0, 0], **warp_args).T
+
+
+def warp_coord_map(img_xyz: np.ndarray, coord_map: np.ndarray, mode: str = 'constant',
+                   cval: float | int = 0.0, scale_xyz: Optional[Sequence[float]] = None,
+                   **warp_args) -> np.ndarray:
+  """Warp by coord map in 3D (decorators/warp.py:221-243).
+
+  coord_map: [3, z, y, x] relative map; `mode` / `cval`: SciPy's boundary mode
+  and fill value, applied to the map interpolation and to the image sample
+  alike (see `warp.ndimage_warp`); scale_xyz: factors for the map's channels;
+  `warp_args` (stride, overlap, order, boxes ...) go to `warp.ndimage_warp`,
+  `work_size` defaults to the image shape.
+  """
+  import scipy.ndimage
+  img_xyz = np.asarray(img_xyz)
+  if img_xyz.ndim != 3:
+    raise RuntimeError('Only 3D images are supported.')
+  warp_args.setdefault('work_size', img_xyz.shape)
+  if scale_xyz is not None:
+    coord_map = coord_map * np.array(scale_xyz).reshape(-1, 1, 1, 1)
+  sampler = functools.partial(scipy.ndimage.map_coordinates, cval=cval, mode=mode)
+  return warp.ndimage_warp(img_xyz.T, coord_map, map_coordinates=sampler, **warp_args).T
+
+
+_warp_affine = warp_affine
+_warp_coord_map = warp_coord_map

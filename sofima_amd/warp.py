@@ -26,6 +26,12 @@ order (sfm_spline_prefilter), and are opt-in (SFM_SPLINE_ORDERS=1).
 `warp_points` (warp.py:541-605) maps point sets through a coordinate map: one
 kernel, every point reads its four map nodes directly, pinned against the
 reference function through the golden shim (tests/golden/mapgeom.npz).
+`ndimage_warp` also takes SciPy's sampler with a boundary mode and a fill value
+(`map_coordinates=functools.partial(scipy.ndimage.map_coordinates, mode=...,
+cval=...)`, as decorators/warp.py calls it), and `affine_transform` is
+scipy.ndimage.affine_transform as one fused kernel that reads no coordinate
+map; both are pinned to SciPy bit for bit (tests/test_gpu_ndwarp_modes.py,
+tests/test_gpu_affine_warp.py).
 render_tiles has no parity contract and stays out of scope.
 """
 from __future__ import annotations
@@ -237,6 +243,39 @@ def warp_subvolume(image: np.ndarray, image_box, coord_map: np.ndarray, map_box,
   return warped.astype(orig_dtype)
 
 
+def _scipy_sampler(map_coordinates):
+  """(mode, cval) of a `map_coordinates` argument that the device reproduces:
+  scipy.ndimage.map_coordinates itself, or a functools.partial of it with no
+  positional arguments and keywords among mode and cval.  None otherwise."""
+  try:
+    import scipy.ndimage
+  except ImportError:
+    return None
+  kw = {}
+  if isinstance(map_coordinates, functools.partial):
+    if map_coordinates.args or not set(map_coordinates.keywords) <= {'mode', 'cval'}:
+      return None
+    kw = map_coordinates.keywords
+    map_coordinates = map_coordinates.func
+  if map_coordinates is not scipy.ndimage.map_coordinates:
+    return None
+  return kw.get('mode', 'constant'), kw.get('cval', 0.0)
+
+
+def _boundary(what: str, mode, cval, order, dtype) -> tuple[int, float]:
+  """(SFM_MODE_*, cval) of SciPy's `mode` / `cval`, or the error of what is not built."""
+  if mode not in _abi.MODES:
+    raise ValueError(f'{what}: boundary mode {mode!r} (one of {sorted(_abi.MODES)})')
+  if order in _spline.ORDERS and mode not in ('constant', 'mirror', 'wrap'):
+    raise NotImplementedError(
+        f'{what}: boundary mode {mode!r} at interpolation order {order} (orders 2 to 5 take '
+        "'constant', 'mirror' and 'wrap'; the other modes need another B-spline prefilter)")
+  cval = float(cval)
+  if np.dtype(dtype).kind != 'f' and not np.isfinite(cval):
+    raise ValueError(f'{what}: cval {cval} for a {np.dtype(dtype)} image')
+  return _abi.MODES[mode], cval
+
+
 def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, overlap,
                  order=1, map_coordinates=None, image_box=None, map_box=None, out_box=None,
                  parallelism: int = 1, out_scale=(1.0, 1.0, 1.0)) -> np.ndarray:
@@ -263,6 +302,17 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
   to 5, with the default `map_coordinates`; without the switch orders above 1
   raise NotImplementedError as they always did; custom samplers and uint64
   label volumes raise it too (use `warp_subvolume` for label volumes).
+
+  `map_coordinates` may be scipy.ndimage.map_coordinates or a functools.partial
+  of it that sets `mode` and / or `cval` (decorators/warp.py:237-242): the
+  kernel then applies that boundary mode and fill value to BOTH steps, as the
+  reference passes the callable to both -- outside the node grid the dense
+  coordinate is `cval` in source voxels (or the folded node value), and the
+  image sample follows the same rule.  Orders 0 and 1 take every mode of SciPy,
+  orders 2 to 5 'constant', 'mirror' and 'wrap'; an integer image needs a
+  finite `cval` and takes it through the conversion of a sampled value.  A NaN
+  coordinate or one of magnitude 2**31 and above gives `cval` (SciPy's result
+  there is an undefined cast, except under 'constant').
   """
   del parallelism
   image = np.asarray(image)
@@ -274,11 +324,21 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
   assert dim == len(work_size)
   if dim != image.ndim:
     raise ValueError(f'Dimension mismatch: image: {image.ndim} vs coord map: {dim}')
+  boundary = None
   if map_coordinates is not None:
-    raise NotImplementedError('ndimage_warp: custom map_coordinates callables run on the host only')
+    boundary = _scipy_sampler(map_coordinates)
+    if boundary is None:
+      raise NotImplementedError(
+          'ndimage_warp: custom map_coordinates callables run on the host only '
+          '(scipy.ndimage.map_coordinates, or a functools.partial of it with mode / cval, '
+          'runs on the device)')
+    if boundary == ('constant', 0.0):
+      boundary = None
   if image.dtype == np.uint64:
     raise NotImplementedError('ndimage_warp: uint64 label volumes (use warp_subvolume)')
   _spline.check_order(order, 'ndimage_warp')
+  if boundary is not None:
+    boundary = _boundary('ndimage_warp', boundary[0], boundary[1], order, image.dtype)
   if dim not in (2, 3):
     raise ValueError(f'ndimage_warp: {dim}-d data')
   if map_box is not None and image_box is None:
@@ -342,9 +402,96 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
     coeffs, _ = _spline.prefilter(
         [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev)
     d.image = coeffs.data_ptr()
-    _abi.check(_abi.load().sfm_ndimage_warp_spline(C.byref(d)))
-  else:
+    if boundary is None:
+      _abi.check(_abi.load().sfm_ndimage_warp_spline(C.byref(d)))
+  elif boundary is None:
     _abi.check(_abi.load().sfm_ndimage_warp(C.byref(d)))
+  if boundary is not None:
+    _abi.check(_abi.load().sfm_ndimage_warp_mode(C.byref(d), boundary[0], boundary[1]))
+  warped = out_t.cpu().numpy()
+  if image.dtype == np.uint16:
+    warped = warped.view(np.uint16)
+  return warped.astype(image.dtype)
+
+
+def _image_dtype(image: np.ndarray, what: str):
+  if image.dtype == np.uint8:
+    return _abi.DTYPE_U8, np.uint8
+  if image.dtype == np.uint16:
+    return _abi.DTYPE_U16, np.int16
+  if image.dtype == np.float32:
+    return _abi.DTYPE_F32, np.float32
+  raise NotImplementedError(f'{what}: {image.dtype} images (uint8, uint16, float32)')
+
+
+def affine_transform(image: np.ndarray, matrix, offset=0.0, order=1, mode='constant',
+                     cval=0.0, output_shape=None, output=None) -> np.ndarray:
+  """scipy.ndimage.affine_transform on the device, 2-D and 3-D, bit for bit.
+
+  image: [z, ] y, x data (uint8 / uint16 / float32); matrix: (dim, dim), with
+  `offset` a scalar or a vector, or (dim, dim + 1) / (dim + 1, dim + 1), whose
+  last column is the offset, as SciPy takes them.  The output has the input's
+  shape and dtype.  One kernel forms the source coordinate of every output voxel
+  from the matrix (products added in axis order, the offset last: SciPy's
+  rounding) and samples the image there; no coordinate map is built.  Orders,
+  the switch for orders 2 to 5, `mode` and `cval` as in `ndimage_warp`.  Not
+  covered: `output_shape`, `output`, and 1-D (diagonal) matrices, which SciPy
+  sends down its separate zoom-and-shift route; they raise NotImplementedError.
+  """
+  image = np.asarray(image)
+  dim = image.ndim
+  if output_shape is not None or output is not None:
+    raise NotImplementedError('affine_transform: output_shape and output')
+  if dim not in (2, 3):
+    raise ValueError(f'affine_transform: {dim}-d data')
+  matrix = np.asarray(matrix, dtype=np.float64)
+  if matrix.ndim == 1:
+    raise NotImplementedError('affine_transform: 1-d (diagonal) matrices')
+  if matrix.shape in ((dim + 1, dim + 1), (dim, dim + 1)):
+    if matrix.shape[0] == dim + 1:
+      expected = [0.0] * dim + [1.0]
+      if not np.all(matrix[dim] == expected):
+        raise ValueError(f'Expected homogeneous transformation matrix with shape '
+                         f'{matrix.shape} for image shape {image.shape}, but bottom row was '
+                         f'not equal to {expected}')
+    offset = matrix[:dim, dim]
+    matrix = matrix[:dim, :dim]
+  elif matrix.shape != (dim, dim):
+    raise RuntimeError(f'affine_transform: matrix shape {matrix.shape} for {dim}-d data')
+  offset = np.asarray(offset, dtype=np.float64)
+  if offset.ndim == 0:
+    offset = np.full(dim, float(offset))
+  if offset.shape != (dim,):
+    raise RuntimeError('offset shape not correct')
+  if image.dtype == np.uint64:
+    raise NotImplementedError('affine_transform: uint64 label volumes')
+  _spline.check_order(order, 'affine_transform')
+  mode_id, cval = _boundary('affine_transform', mode, cval, order, image.dtype)
+  dtype, view = _image_dtype(image, 'affine_transform')
+
+  dev = _dev.device()
+  img_t = torch.from_numpy(np.ascontiguousarray(image).view(view)).to(dev)
+  out_t = torch.empty(image.shape, dtype=img_t.dtype, device=dev)
+  shape = (1,) * (3 - dim) + tuple(image.shape)
+  full = np.zeros((3, 3), np.float64)
+  full[3 - dim:, 3 - dim:] = matrix
+  d = _abi.SfmAffineWarpDesc()
+  d.ndim = dim
+  d.dtype = dtype
+  d.order = int(order)
+  d.mode = mode_id
+  d.shape = (C.c_int32 * 3)(*shape)
+  d.matrix = (C.c_double * 9)(*full.ravel())
+  d.offset = (C.c_double * 3)(*((0.0,) * (3 - dim) + tuple(float(v) for v in offset)))
+  d.cval = cval
+  d.image = img_t.data_ptr()
+  d.out = out_t.data_ptr()
+  d.stream = _dev.stream_ptr()
+  if order in _spline.ORDERS:
+    coeffs, _ = _spline.prefilter(
+        [(img_t.data_ptr(), shape, (shape[1] * shape[2], shape[2], 1))], dtype, order, dev)
+    d.image = coeffs.data_ptr()
+  _abi.check(_abi.load().sfm_affine_warp(C.byref(d)))
   warped = out_t.cpu().numpy()
   if image.dtype == np.uint16:
     warped = warped.view(np.uint16)
