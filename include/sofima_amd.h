@@ -45,7 +45,8 @@ extern "C" {
                                    sfm_render_tiles3d, and sfm_spline_prefilter,
                                    sfm_ndimage_warp_spline and
                                    sfm_render_tiles3d_spline, and
-                                   sfm_ndimage_warp_mode and sfm_affine_warp */
+                                   sfm_ndimage_warp_mode and sfm_affine_warp, and
+                                   sfm_ndimage_warp_rel */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -821,6 +822,48 @@ typedef struct SfmAffineWarpDesc {
 } SfmAffineWarpDesc;
 
 int sfm_affine_warp(const SfmAffineWarpDesc* desc);
+
+/* sfm_ndimage_warp, _spline and _mode on the RELATIVE coordinate map, float32 or
+ * float64, as the map functions of this library leave it on the device: no
+ * absolute float64 copy is prepared.  Every node a tap reads becomes the absolute
+ * source coordinate in registers, with the roundings of the reference's NumPy
+ * statements (warp.py:249-262).  For channel c (x, y[, z]; its axis is
+ * ndim - 1 - c), node index n along that axis and map type M:
+ *   v = (double)(M)((double)rel[c][node] + (double)n * stride[axis])
+ *   v = (double)(M)(v + shift[c])         only if has_shift: a map_box was given
+ *   v = v * scale[c]
+ * n * stride is one rounded double product.  The rest is sfm_ndimage_warp: the
+ * same kernels with another map accessor, bit for bit the result of the absolute
+ * entries on the map those statements produce.  order 0 .. 5 (2 .. 5: `image`
+ * holds the float64 B-spline coefficients, dtype is the type of `out` alone);
+ * the boundary fields are read only if has_boundary, as sfm_ndimage_warp_mode
+ * reads its arguments. */
+typedef struct SfmNdWarpRelDesc {
+  int32_t ndim;                 /* 2 or 3                                      */
+  int32_t dtype;                /* SFM_DTYPE_U8 | U16 | F32 of image and out   */
+  int32_t order;                /* 0 .. 5                                      */
+  int32_t image_shape[3];       /* z, y, x                                     */
+  int32_t map_shape[3];         /* z, y, x nodes                               */
+  int32_t out_shape[3];         /* z, y, x                                     */
+  double stride[3];             /* z, y, x output voxels per map node          */
+  double offset[3];             /* z, y, x of map node 0 relative to out voxel 0 */
+  double shift[3];              /* per channel x, y, z: map_box.start[c] *
+                                   stride of the channel's axis -
+                                   image_box.start[c] / out_scale[c]           */
+  double scale[3];              /* per channel x, y, z: out_scale              */
+  double cval;                  /* fill value, if has_boundary                 */
+  int32_t map_f64;              /* 0: rel_map is float32, else float64         */
+  int32_t has_shift;            /* 0: the shift is not added at all            */
+  int32_t has_boundary;         /* 0: mode "constant", cval 0                  */
+  int32_t mode;                 /* SFM_MODE_*, if has_boundary                 */
+  const void* image;            /* device [z, y, x]                            */
+  const void* rel_map;          /* device [ndim, z, y, x], channels x, y[, z]:
+                                   relative coordinates                        */
+  void* out;                    /* device [z, y, x]                            */
+  void* stream;
+} SfmNdWarpRelDesc;
+
+int sfm_ndimage_warp_rel(const SfmNdWarpRelDesc* desc);
 
 /* ------------------------------------------------------------------------
  * Map geometry: the one-pass helpers that the reference's renderers call

@@ -316,6 +316,30 @@ class SfmAffineWarpDesc(C.Structure):
   ]
 
 
+class SfmNdWarpRelDesc(C.Structure):
+  _fields_ = [
+      ('ndim', i32),
+      ('dtype', i32),
+      ('order', i32),
+      ('image_shape', i32 * 3),
+      ('map_shape', i32 * 3),
+      ('out_shape', i32 * 3),
+      ('stride', C.c_double * 3),
+      ('offset', C.c_double * 3),
+      ('shift', C.c_double * 3),
+      ('scale', C.c_double * 3),
+      ('cval', C.c_double),
+      ('map_f64', i32),
+      ('has_shift', i32),
+      ('has_boundary', i32),
+      ('mode', i32),
+      ('image', C.c_void_p),
+      ('rel_map', C.c_void_p),
+      ('out', C.c_void_p),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmRenderTile(C.Structure):
   _fields_ = [
       ('image', C.c_void_p),
@@ -652,6 +676,7 @@ SIGNATURES = {
     'sfm_render_tiles3d_spline': (C.c_int, [C.POINTER(SfmRenderTilesDesc), C.c_void_p]),
     'sfm_ndimage_warp_mode': (C.c_int, [C.POINTER(SfmNdWarpDesc), i32, C.c_double]),
     'sfm_affine_warp': (C.c_int, [C.POINTER(SfmAffineWarpDesc)]),
+    'sfm_ndimage_warp_rel': (C.c_int, [C.POINTER(SfmNdWarpRelDesc)]),
     'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),
     'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
     'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),

@@ -10,7 +10,8 @@
 // from SciPy's behaviour in tests/ndwarp_modes_ref.py.
 //
 // `a` is anything indexable by a linear element offset whose elements widen to
-// double: a pointer, or a view such as ShiftedMap below.  `shape` holds 3
+// double: a pointer, or a view such as ShiftedMap below; linear_sample also takes
+// a view whose value depends on the tap's node indices (RelativeMap).  `shape` holds 3
 // entries (z, y, x; the last DIM are used) and is what coordinates are tested
 // against.  `pitch`, when given, holds the element distance per axis in the same
 // layout: a region of a larger array is then sampled in place (the region's
@@ -128,6 +129,22 @@ __device__ __forceinline__ long long fold_tap(int mode, int len, long long i, bo
   }
 }
 
+// The element of `a` at linear offset `idx`, widened to double.  `node` holds the
+// folded tap index per axis (DIM entries), which linear_sample has at hand: an
+// accessor whose value depends on the tap's position (RelativeMap below) declares
+// at(idx, node) and gets it without recovering it from `idx`; everything else is
+// read as a[idx] and the indices fall away unused.
+template <typename A>
+__device__ __forceinline__ auto tap_value(const A& a, long long idx, const long long* node)
+    -> decltype(a.at(idx, node)) {
+  return a.at(idx, node);
+}
+template <typename A>
+__device__ __forceinline__ auto tap_value(const A& a, long long idx, const long long*)
+    -> decltype(static_cast<double>(a[idx])) {
+  return static_cast<double>(a[idx]);
+}
+
 // scipy NI_GeometricTransform, order 1, mode "constant", cval 0: outside
 // [0, len - 1] on any axis, NaN included -> 0; the tap beyond the last sample
 // (coordinate exactly len - 1) carries weight 0 and is read mirrored, from
@@ -167,6 +184,7 @@ __device__ __forceinline__ double linear_sample(const A a, const int* shape, con
 #pragma unroll
   for (int tap = 0; tap < (1 << DIM); ++tap) {
     long long idx = 0;
+    long long node[DIM];
     bool fill = false;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) {
@@ -180,9 +198,10 @@ __device__ __forceinline__ double linear_sample(const A a, const int* shape, con
       } else {
         if (i > len - 1) i = len > 1 ? len - 2 : 0;
       }
+      node[d] = i;
       idx += i * step[d];
     }
-    double coeff = fill ? b.cval : static_cast<double>(a[idx]);
+    double coeff = fill ? b.cval : tap_value(a, idx, node);
 #pragma unroll
     for (int d = 0; d < DIM; ++d) coeff = coeff * w[d][(tap >> (DIM - 1 - d)) & 1];
     acc = acc + coeff;
@@ -368,6 +387,33 @@ struct ShiftedMap {
   const double* m;
   double shift;
   __device__ __forceinline__ double operator[](long long i) const { return m[i] + shift; }
+};
+
+// One channel of a RELATIVE coordinate map of type M (float or double), read as the
+// absolute source coordinate the reference's NumPy statements form from it
+// (warp.py:249-262): to_absolute adds node x stride in place -- computed in
+// double, stored as M --, the box shift is a second in-place add, stored as M
+// again, and the out_scale product is float64:
+//   v = (double)(M)(rel + (double)node[axis] * stride)
+//   v = (double)(M)(v + shift)        only with a map_box (-0.0 + 0.0 is +0.0)
+//   v = v * scale
+// node x stride is one rounded product (no contraction with the add).  `axis` is
+// the channel's own axis among the DIM entries of `node`.
+template <typename M, int DIM>
+struct RelativeMap {
+  const M* m;
+  int axis;
+  bool has_shift;
+  double stride, shift, scale;
+  __device__ __forceinline__ double at(long long i, const long long* node) const {
+    long long n = node[0];   // a select per axis, not an indexed read of registers
+#pragma unroll
+    for (int k = 1; k < DIM; ++k) n = axis == k ? node[k] : n;
+    const double off = static_cast<double>(n) * stride;
+    double v = static_cast<double>(static_cast<M>(static_cast<double>(m[i]) + off));
+    if (has_shift) v = static_cast<double>(static_cast<M>(v + shift));
+    return v * scale;
+  }
 };
 
 }  // namespace sfm

@@ -185,13 +185,44 @@ extern "C" int sfm_warp_section(const SfmWarpDesc* d) {
 // order 1 on the float64 source map at the node-space position of the output
 // voxel, then order 0 / 1 on the image at the resulting coordinates, or order
 // 2 .. 5 on its B-spline coefficients (sfm_spline_prefilter).  Double arithmetic
-// in SciPy's order (this file is built with -ffp-contract=off).
+// in SciPy's order (this file is built with -ffp-contract=off).  The source map
+// is either the float64 absolute map a caller prepared, or the relative map in
+// its own type, made absolute on every read (sfm_ndimage_warp_rel): one kernel
+// template, two map accessors.
 // ---------------------------------------------------------------------------
 namespace {
 
+// The map of a launch, as the kernels read it: channel<DIM>(d, nodes, stride) is
+// the accessor of the channel that gives the dense coordinate of axis d (channel
+// DIM - 1 - d: channels are x, y[, z]) for sfm::linear_sample.
+//
+// AbsoluteMap: the float64 absolute source map that the caller prepared.
+struct AbsoluteMap {
+  const double* m;
+  template <int DIM>
+  __device__ __forceinline__ const double* channel(int d, long long nodes, const double*) const {
+    return m + (long long)(DIM - 1 - d) * nodes;
+  }
+};
+// RelativeMapArgs: the relative map in its own type; the absolute value of a node
+// is formed on every read (sfm::RelativeMap).  shift and scale are per channel.
+template <typename M>
+struct RelativeMapArgs {
+  const M* m;
+  int has_shift;
+  double shift[3], scale[3];
+  template <int DIM>
+  __device__ __forceinline__ sfm::RelativeMap<M, DIM> channel(int d, long long nodes,
+                                                              const double* stride) const {
+    const int c = DIM - 1 - d;
+    return {m + (long long)c * nodes, d, has_shift != 0, stride[3 - DIM + d], shift[c], scale[c]};
+  }
+};
+
+template <typename MAP>
 struct NdWarpArgs {
   const void* image;
-  const double* map;
+  MAP map;
   void* out;
   int order;
   int ishape[3], mshape[3], oshape[3];
@@ -200,8 +231,8 @@ struct NdWarpArgs {
 
 // ORDER 0: a.order (0 or 1) on the image; ORDER 2 .. 5: a.image holds the float64
 // B-spline coefficients of the image (sfm_spline_prefilter).
-template <int DIM, typename T, int ORDER = 0>
-__global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
+template <int DIM, typename T, int ORDER, typename MAP>
+__global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs<MAP> a) {
   const long long n = (long long)a.oshape[0] * a.oshape[1] * a.oshape[2];
   const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
   if (i >= n) return;
@@ -221,7 +252,8 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
   double dense[DIM];
 #pragma unroll
   for (int d = 0; d < DIM; ++d)
-    dense[d] = sfm::linear_sample<DIM>(a.map + (long long)(DIM - 1 - d) * nodes, a.mshape, pos);
+    dense[d] = sfm::linear_sample<DIM>(a.map.template channel<DIM>(d, nodes, a.stride), a.mshape,
+                                       pos);
   double v;
   if constexpr (ORDER >= 2) {
     v = sfm::spline_sample<DIM, ORDER>(static_cast<const double*>(a.image), a.ishape, dense);
@@ -239,8 +271,9 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs a) {
 // the node grid the dense coordinate is cval (in source voxels) or the folded
 // node value, and the image sample follows the same rule; an integer image takes
 // cval through nd_convert like a sampled value.
-template <int DIM, typename T, int ORDER = 0>
-__global__ void __launch_bounds__(kBlock) ndimage_warp_mode_kernel(NdWarpArgs a, sfm::Boundary b) {
+template <int DIM, typename T, int ORDER, typename MAP>
+__global__ void __launch_bounds__(kBlock)
+ndimage_warp_mode_kernel(NdWarpArgs<MAP> a, sfm::Boundary b) {
   const long long n = (long long)a.oshape[0] * a.oshape[1] * a.oshape[2];
   const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
   if (i >= n) return;
@@ -258,8 +291,8 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_mode_kernel(NdWarpArgs a,
   double dense[DIM];
 #pragma unroll
   for (int d = 0; d < DIM; ++d)
-    dense[d] = sfm::linear_sample<DIM, true>(a.map + (long long)(DIM - 1 - d) * nodes, a.mshape,
-                                             pos, nullptr, b);
+    dense[d] = sfm::linear_sample<DIM, true>(a.map.template channel<DIM>(d, nodes, a.stride),
+                                             a.mshape, pos, nullptr, b);
   double v;
   if constexpr (ORDER >= 2) {
     v = sfm::spline_sample<DIM, ORDER, true>(static_cast<const double*>(a.image), a.ishape,
@@ -296,8 +329,14 @@ namespace {
 // the checks and the launch of sfm_ndimage_warp (orders 0, 1 on the image),
 // sfm_ndimage_warp_spline (orders 2 .. 5 on coefficients) and, with a Boundary,
 // sfm_ndimage_warp_mode (either)
-int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline, const sfm::Boundary* bnd = nullptr) {
-  if (!d || !d->image || !d->src_map || !d->out)
+//
+// D is SfmNdWarpDesc with MAP = AbsoluteMap, or SfmNdWarpRelDesc (sfm_ndimage_warp_rel)
+// with MAP = RelativeMapArgs<float | double>: the two descriptors name the fields
+// read here alike, and `map` is checked and filled by the caller.
+template <typename D, typename MAP>
+int ndimage_warp_launch(const D* d, const MAP& map, bool spline,
+                        const sfm::Boundary* bnd = nullptr) {
+  if (!d || !d->image || !map.m || !d->out)
     return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: NULL argument");
   if (d->ndim != 2 && d->ndim != 3) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: ndim %d", d->ndim);
   if (!spline && d->order != 0 && d->order != 1)
@@ -306,9 +345,9 @@ int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline, const sfm::Boundary
   if (spline && (d->order < 2 || d->order > 5))
     return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_spline: interpolation order %d (2 .. 5)",
                      d->order);
-  NdWarpArgs a;
+  NdWarpArgs<MAP> a;
   a.image = d->image;
-  a.map = d->src_map;
+  a.map = map;
   a.out = d->out;
   a.order = d->order;
   long long n = 1;
@@ -334,13 +373,13 @@ int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline, const sfm::Boundary
 #define SFM_NDW_ORDER(T, ORDER)                                                    \
   do {                                                                             \
     if (bnd && d->ndim == 2)                                                       \
-      hipLaunchKernelGGL((ndimage_warp_mode_kernel<2, T, ORDER>), g, b, 0, st, a, *bnd); \
+      hipLaunchKernelGGL((ndimage_warp_mode_kernel<2, T, ORDER, MAP>), g, b, 0, st, a, *bnd); \
     else if (bnd)                                                                  \
-      hipLaunchKernelGGL((ndimage_warp_mode_kernel<3, T, ORDER>), g, b, 0, st, a, *bnd); \
+      hipLaunchKernelGGL((ndimage_warp_mode_kernel<3, T, ORDER, MAP>), g, b, 0, st, a, *bnd); \
     else if (d->ndim == 2)                                                         \
-      hipLaunchKernelGGL((ndimage_warp_kernel<2, T, ORDER>), g, b, 0, st, a);      \
+      hipLaunchKernelGGL((ndimage_warp_kernel<2, T, ORDER, MAP>), g, b, 0, st, a);      \
     else                                                                           \
-      hipLaunchKernelGGL((ndimage_warp_kernel<3, T, ORDER>), g, b, 0, st, a);      \
+      hipLaunchKernelGGL((ndimage_warp_kernel<3, T, ORDER, MAP>), g, b, 0, st, a);      \
   } while (0)
 #define SFM_NDW(T)                                                                 \
   do {                                                                             \
@@ -366,10 +405,12 @@ int ndimage_warp_launch(const SfmNdWarpDesc* d, bool spline, const sfm::Boundary
 
 }  // namespace
 
-extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) { return ndimage_warp_launch(d, false); }
+extern "C" int sfm_ndimage_warp(const SfmNdWarpDesc* d) {
+  return ndimage_warp_launch(d, AbsoluteMap{d ? d->src_map : nullptr}, false);
+}
 
 extern "C" int sfm_ndimage_warp_spline(const SfmNdWarpDesc* d) {
-  return ndimage_warp_launch(d, true);
+  return ndimage_warp_launch(d, AbsoluteMap{d ? d->src_map : nullptr}, true);
 }
 
 extern "C" int sfm_ndimage_warp_mode(const SfmNdWarpDesc* d, int32_t mode, double cval) {
@@ -381,7 +422,40 @@ extern "C" int sfm_ndimage_warp_mode(const SfmNdWarpDesc* d, int32_t mode, doubl
   sfm::Boundary b;
   b.mode = mode;
   b.cval = cval;
-  return ndimage_warp_launch(d, d->order >= 2, &b);
+  return ndimage_warp_launch(d, AbsoluteMap{d->src_map}, d->order >= 2, &b);
+}
+
+namespace {
+
+template <typename M>
+int ndimage_warp_rel_launch(const SfmNdWarpRelDesc* d, const sfm::Boundary* bnd) {
+  RelativeMapArgs<M> map;
+  map.m = static_cast<const M*>(d->rel_map);
+  map.has_shift = d->has_shift ? 1 : 0;
+  for (int c = 0; c < 3; ++c) {
+    map.shift[c] = d->shift[c];
+    map.scale[c] = d->scale[c];
+  }
+  return ndimage_warp_launch(d, map, d->order >= 2, bnd);
+}
+
+}  // namespace
+
+extern "C" int sfm_ndimage_warp_rel(const SfmNdWarpRelDesc* d) {
+  if (!d) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_rel: NULL argument");
+  if (d->order < 0 || d->order > 5)
+    return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_rel: interpolation order %d (0 .. 5)",
+                     d->order);
+  sfm::Boundary b;
+  if (d->has_boundary) {
+    if (int rc = check_boundary("ndimage_warp_rel", d->mode, d->cval, d->order, d->dtype))
+      return rc;
+    b.mode = d->mode;
+    b.cval = d->cval;
+  }
+  const sfm::Boundary* bnd = d->has_boundary ? &b : nullptr;
+  return d->map_f64 ? ndimage_warp_rel_launch<double>(d, bnd)
+                    : ndimage_warp_rel_launch<float>(d, bnd);
 }
 
 // ---------------------------------------------------------------------------

@@ -32,6 +32,13 @@ cval=...)`, as decorators/warp.py calls it), and `affine_transform` is
 scipy.ndimage.affine_transform as one fused kernel that reads no coordinate
 map; both are pinned to SciPy bit for bit (tests/test_gpu_ndwarp_modes.py,
 tests/test_gpu_affine_warp.py).
+`ndimage_warp` and `affine_transform` take resident images (CUDA tensors,
+DeviceArrays) and return DeviceArrays on request, and `ndimage_warp` reads a
+float32 / float64 coordinate map RELATIVE, in its own dtype and where it lies
+(`sfm_ndimage_warp_rel`): the kernel forms the absolute source coordinate of each
+node it reads, with the roundings of the reference's NumPy statements, so
+invert_map / compose_maps_fast / make_affine_map -> ndimage_warp is one device
+chain with no host copy of the map (tests/test_gpu_warp_device.py).
 render_tiles has no parity contract and stays out of scope.
 """
 from __future__ import annotations
@@ -151,7 +158,9 @@ def warp_subvolume(image: np.ndarray, image_box, coord_map: np.ndarray, map_box,
   `.start` / `.size` in xyz (or (start, size) pairs); `stride`: image pixels
   per map node.  Sections whose map is all NaN are skipped (left zero).
   `parallelism` is accepted for compatibility: sections are enqueued back to
-  back on the GPU.
+  back on the GPU.  Image and map are host arrays and the result is one: this
+  OpenCV-semantics path is not part of the resident chain that `ndimage_warp`
+  and `affine_transform` serve (it prepares its absolute map on the host).
   """
   del parallelism
   dev = _dev.device()
@@ -276,15 +285,79 @@ def _boundary(what: str, mode, cval, order, dtype) -> tuple[int, float]:
   return _abi.MODES[mode], cval
 
 
-def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, overlap,
+_TORCH_DTYPES = {torch.uint8: np.uint8, torch.uint16: np.uint16, torch.float32: np.float32,
+                 torch.float64: np.float64, torch.uint64: np.uint64}
+
+
+def _resident(x):
+  """The tensor of a DeviceArray or CUDA tensor; a NumPy array of anything else (a
+  CPU tensor is host data like an array)."""
+  if isinstance(x, _dev.DeviceArray):
+    x = x.tensor
+  if isinstance(x, torch.Tensor):
+    return x if x.is_cuda else x.numpy()
+  return np.asarray(x)
+
+
+def _np_dtype(x, what: str) -> np.dtype:
+  """NumPy dtype of an array or of a device tensor."""
+  if not isinstance(x, torch.Tensor):
+    return x.dtype
+  if x.dtype not in _TORCH_DTYPES:
+    raise NotImplementedError(f'{what}: {x.dtype} device tensors')
+  return np.dtype(_TORCH_DTYPES[x.dtype])
+
+
+def _image_tensor(image, view, dev) -> torch.Tensor:
+  """Contiguous device tensor of an image; uint16 is held as int16, the type torch
+  has kernels for (a view: the library reads the bits as unsigned)."""
+  if isinstance(image, torch.Tensor):
+    if image.dtype == torch.uint16:
+      image = image.view(torch.int16)
+    return image.to(dev).contiguous()
+  return torch.from_numpy(np.ascontiguousarray(image).view(view)).to(dev)
+
+
+def _warped(out_t: torch.Tensor, dtype: np.dtype, device_output: bool):
+  """The result as a DeviceArray of the image's dtype, or downloaded."""
+  if device_output:
+    return _dev.DeviceArray(out_t.view(torch.uint16) if dtype == np.uint16 else out_t)
+  warped = out_t.cpu().numpy()
+  if dtype == np.uint16:
+    warped = warped.view(np.uint16)
+  return warped.astype(dtype)
+
+
+def _transpose_resident(t: torch.Tensor) -> torch.Tensor:
+  """Axes reversed (xyz <-> zyx) on the device, contiguous."""
+  if t.dtype == torch.uint16:
+    return t.view(torch.int16).permute(*reversed(range(t.ndim))).contiguous().view(torch.uint16)
+  return t.permute(*reversed(range(t.ndim))).contiguous()
+
+
+def ndimage_warp(image, coord_map, stride, work_size, overlap,
                  order=1, map_coordinates=None, image_box=None, map_box=None, out_box=None,
-                 parallelism: int = 1, out_scale=(1.0, 1.0, 1.0)) -> np.ndarray:
+                 parallelism: int = 1, out_scale=(1.0, 1.0, 1.0),
+                 device_output: bool | None = None):
   """Warps a subvolume of data using map_coordinates semantics (warp.py:189-335).
 
   image: [z, ] y, x data (uint8 / uint16 / float32); coord_map: [N, [z,] y, x]
   relative coordinate map; stride: [z,] y, x image voxels per map node;
   image_box / map_box / out_box: objects with `.start` / `.size` in xyz (or
   (start, size) pairs); out_scale: xy[z] out_voxel / source_voxel.
+
+  `image` and `coord_map` may each be a NumPy array, a CUDA torch tensor or a
+  DeviceArray (a CPU tensor counts as an array); device images are uint8, uint16
+  or float32 tensors.  device_output: True returns a DeviceArray of the image's
+  dtype, False a NumPy array, None (the default) follows the image.  A float32 or
+  float64 map is read RELATIVE and in its own dtype (`sfm_ndimage_warp_rel`): a
+  NumPy map is uploaded once as it is, a resident one is read where it lies, and
+  the kernel forms the absolute source coordinate of every node it reads with
+  the reference's roundings.  With image and map resident and a
+  device output the call copies nothing to the host and does not wait for the
+  compute stream (orders 2 to 5 upload the prefilter's table on a side stream).
+  A NumPy map of another dtype is made absolute on the host in NumPy's own
+  arithmetic, as before; a resident map of another dtype raises TypeError.
 
   One kernel computes, per output voxel, what the reference computes with two
   rounds of scipy.ndimage.map_coordinates per work box (dense coordinates by
@@ -315,9 +388,10 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
   there is an undefined cast, except under 'constant').
   """
   del parallelism
-  image = np.asarray(image)
-  coord_map = np.asarray(coord_map)
-  shape = coord_map.shape[1:]
+  image = _resident(image)
+  coord_map = _resident(coord_map)
+  img_dtype = _np_dtype(image, 'ndimage_warp')
+  shape = tuple(coord_map.shape[1:])
   dim = len(shape)
   assert dim == len(stride)
   assert dim == len(overlap)
@@ -334,18 +408,107 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
           'runs on the device)')
     if boundary == ('constant', 0.0):
       boundary = None
-  if image.dtype == np.uint64:
+  if img_dtype == np.uint64:
     raise NotImplementedError('ndimage_warp: uint64 label volumes (use warp_subvolume)')
   _spline.check_order(order, 'ndimage_warp')
   if boundary is not None:
-    boundary = _boundary('ndimage_warp', boundary[0], boundary[1], order, image.dtype)
+    boundary = _boundary('ndimage_warp', boundary[0], boundary[1], order, img_dtype)
   if dim not in (2, 3):
     raise ValueError(f'ndimage_warp: {dim}-d data')
   if map_box is not None and image_box is None:
     raise ValueError('image_box has to be specified when map_box is used.')
+  if isinstance(coord_map, torch.Tensor) and coord_map.dtype not in (torch.float32,
+                                                                     torch.float64):
+    raise TypeError(f'ndimage_warp: {coord_map.dtype} device maps (float32, float64)')
 
-  # absolute source map, operation for operation (map_utils.to_absolute adds in
-  # place in the map's dtype; the out_scale product is float64): warp.py:250-265
+  # The absolute source map (warp.py:250-265) is formed by the kernel from the
+  # relative one, with NumPy's roundings, when those are the ones of a float32 /
+  # float64 map and a float64 out_scale product; any other map is made absolute
+  # here in NumPy's own arithmetic.
+  scale = np.array(out_scale[:dim])
+  map_dtype = _np_dtype(coord_map, 'ndimage_warp')
+  relative = (map_dtype in (np.float32, np.float64) and scale.dtype.kind in 'iuf' and
+              np.result_type(map_dtype, scale.dtype) == np.float64)
+  shift = None
+  if relative and map_box is not None:
+    map_start, _ = _box(map_box)
+    img_start, _ = _box(image_box)
+    shift = np.asarray(map_start[:dim] * np.asarray(stride)[::-1] -
+                       img_start[:dim] / np.asarray(out_scale)[:dim], dtype=np.float64)
+  if not relative:
+    if isinstance(coord_map, torch.Tensor):
+      coord_map = coord_map.cpu().numpy()
+    coord_map = _absolute_map(coord_map, stride, image_box, map_box, out_scale)
+
+  if out_box is not None:
+    out_start, out_size = _box(out_box)
+    out_shape = tuple(int(v) for v in np.asarray(out_size)[::-1][-dim:])
+  else:
+    out_start = np.zeros(3, np.int64)
+    out_shape = tuple(image.shape)
+  if map_box is not None:
+    map_start, _ = _box(map_box)
+    offset = (map_start * np.asarray(stride)[::-1] - out_start)[::-1]
+  else:
+    offset = (0,) * dim
+
+  dtype, view = _image_dtype(img_dtype, 'ndimage_warp')
+  if device_output is None:
+    device_output = isinstance(image, torch.Tensor)
+  dev = _dev.device()
+  img_t = _image_tensor(image, view, dev)
+  if isinstance(coord_map, torch.Tensor):
+    map_t = coord_map.to(dev).contiguous()
+  else:
+    map_t = torch.from_numpy(np.ascontiguousarray(coord_map)).to(dev)
+  out_t = torch.empty(out_shape, dtype=img_t.dtype, device=dev)
+  pad = (1,) * (3 - dim)
+  d = _abi.SfmNdWarpRelDesc() if relative else _abi.SfmNdWarpDesc()
+  d.ndim = dim
+  d.dtype = dtype
+  d.order = int(order)
+  d.image_shape = (C.c_int32 * 3)(*(pad + tuple(image.shape)))
+  d.map_shape = (C.c_int32 * 3)(*(pad + shape))
+  d.out_shape = (C.c_int32 * 3)(*(pad + out_shape))
+  d.stride = (C.c_double * 3)(*((1.0,) * (3 - dim) + tuple(float(v) for v in stride)))
+  d.offset = (C.c_double * 3)(*((0.0,) * (3 - dim) + tuple(float(v) for v in offset[-dim:])))
+  d.image = img_t.data_ptr()
+  d.out = out_t.data_ptr()
+  d.stream = _dev.stream_ptr()
+  if order in _spline.ORDERS:
+    ishape = pad + tuple(image.shape)
+    coeffs, _ = _spline.prefilter(
+        [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev)
+    d.image = coeffs.data_ptr()
+  lib = _abi.load()
+  if relative:
+    d.rel_map = map_t.data_ptr()
+    d.map_f64 = int(map_dtype == np.float64)
+    d.scale = (C.c_double * 3)(*(tuple(float(v) for v in scale) + (1.0,) * (3 - dim)))
+    if shift is not None:
+      d.has_shift = 1
+      d.shift = (C.c_double * 3)(*(tuple(float(v) for v in shift) + (0.0,) * (3 - dim)))
+    if boundary is not None:
+      d.has_boundary = 1
+      d.mode, d.cval = boundary
+    _abi.check(lib.sfm_ndimage_warp_rel(C.byref(d)))
+  else:
+    d.src_map = map_t.data_ptr()
+    if boundary is not None:
+      _abi.check(lib.sfm_ndimage_warp_mode(C.byref(d), boundary[0], boundary[1]))
+    elif order in _spline.ORDERS:
+      _abi.check(lib.sfm_ndimage_warp_spline(C.byref(d)))
+    else:
+      _abi.check(lib.sfm_ndimage_warp(C.byref(d)))
+  return _warped(out_t, img_dtype, device_output)
+
+
+def _absolute_map(coord_map: np.ndarray, stride, image_box, map_box, out_scale) -> np.ndarray:
+  """The float64 absolute source map on the host, operation for operation
+  (map_utils.to_absolute adds in place in the map's dtype; the out_scale product
+  is NumPy's): warp.py:250-265.  For the maps the kernel does not read relative."""
+  shape = coord_map.shape[1:]
+  dim = len(shape)
   src = np.array(coord_map, copy=True)
   idx = np.mgrid[tuple(slice(0, s) for s in shape)]
   off_zyx = [h * st for h, st in zip(idx, stride)]
@@ -357,75 +520,22 @@ def ndimage_warp(image: np.ndarray, coord_map: np.ndarray, stride, work_size, ov
     src += (map_start[:dim] * np.asarray(stride)[::-1] -
             img_start[:dim] / np.asarray(out_scale)[:dim]).reshape((dim,) + (1,) * dim)
   reshaper = (slice(None),) + (np.newaxis,) * dim
-  src = np.ascontiguousarray(src.copy() * np.array(out_scale[:dim])[reshaper], dtype=np.float64)
-
-  if out_box is not None:
-    out_start, out_size = _box(out_box)
-    out_shape = tuple(int(v) for v in np.asarray(out_size)[::-1][-dim:])
-  else:
-    out_start = np.zeros(3, np.int64)
-    out_shape = image.shape
-  if map_box is not None:
-    map_start, _ = _box(map_box)
-    offset = (map_start * np.asarray(stride)[::-1] - out_start)[::-1]
-  else:
-    offset = (0,) * dim
-
-  if image.dtype == np.uint8:
-    dtype, view = _abi.DTYPE_U8, np.uint8
-  elif image.dtype == np.uint16:
-    dtype, view = _abi.DTYPE_U16, np.int16
-  elif image.dtype == np.float32:
-    dtype, view = _abi.DTYPE_F32, np.float32
-  else:
-    raise NotImplementedError(f'ndimage_warp: {image.dtype} images (uint8, uint16, float32)')
-  dev = _dev.device()
-  img_t = torch.from_numpy(np.ascontiguousarray(image).view(view)).to(dev)
-  map_t = torch.from_numpy(src).to(dev)
-  out_t = torch.empty(out_shape, dtype=img_t.dtype, device=dev)
-  pad = (1,) * (3 - dim)
-  d = _abi.SfmNdWarpDesc()
-  d.ndim = dim
-  d.dtype = dtype
-  d.order = int(order)
-  d.image_shape = (C.c_int32 * 3)(*(pad + tuple(image.shape)))
-  d.map_shape = (C.c_int32 * 3)(*(pad + tuple(shape)))
-  d.out_shape = (C.c_int32 * 3)(*(pad + tuple(out_shape)))
-  d.stride = (C.c_double * 3)(*((1.0,) * (3 - dim) + tuple(float(v) for v in stride)))
-  d.offset = (C.c_double * 3)(*((0.0,) * (3 - dim) + tuple(float(v) for v in offset[-dim:])))
-  d.image = img_t.data_ptr()
-  d.src_map = map_t.data_ptr()
-  d.out = out_t.data_ptr()
-  d.stream = _dev.stream_ptr()
-  if order in _spline.ORDERS:
-    ishape = pad + tuple(image.shape)
-    coeffs, _ = _spline.prefilter(
-        [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev)
-    d.image = coeffs.data_ptr()
-    if boundary is None:
-      _abi.check(_abi.load().sfm_ndimage_warp_spline(C.byref(d)))
-  elif boundary is None:
-    _abi.check(_abi.load().sfm_ndimage_warp(C.byref(d)))
-  if boundary is not None:
-    _abi.check(_abi.load().sfm_ndimage_warp_mode(C.byref(d), boundary[0], boundary[1]))
-  warped = out_t.cpu().numpy()
-  if image.dtype == np.uint16:
-    warped = warped.view(np.uint16)
-  return warped.astype(image.dtype)
+  return np.ascontiguousarray(src.copy() * np.array(out_scale[:dim])[reshaper], dtype=np.float64)
 
 
-def _image_dtype(image: np.ndarray, what: str):
-  if image.dtype == np.uint8:
+def _image_dtype(dtype: np.dtype, what: str):
+  """(_abi.DTYPE_*, the NumPy type the bits are uploaded as) of an image dtype."""
+  if dtype == np.uint8:
     return _abi.DTYPE_U8, np.uint8
-  if image.dtype == np.uint16:
+  if dtype == np.uint16:
     return _abi.DTYPE_U16, np.int16
-  if image.dtype == np.float32:
+  if dtype == np.float32:
     return _abi.DTYPE_F32, np.float32
-  raise NotImplementedError(f'{what}: {image.dtype} images (uint8, uint16, float32)')
+  raise NotImplementedError(f'{what}: {dtype} images (uint8, uint16, float32)')
 
 
-def affine_transform(image: np.ndarray, matrix, offset=0.0, order=1, mode='constant',
-                     cval=0.0, output_shape=None, output=None) -> np.ndarray:
+def affine_transform(image, matrix, offset=0.0, order=1, mode='constant', cval=0.0,
+                     output_shape=None, output=None, device_output: bool | None = None):
   """scipy.ndimage.affine_transform on the device, 2-D and 3-D, bit for bit.
 
   image: [z, ] y, x data (uint8 / uint16 / float32); matrix: (dim, dim), with
@@ -437,8 +547,11 @@ def affine_transform(image: np.ndarray, matrix, offset=0.0, order=1, mode='const
   the switch for orders 2 to 5, `mode` and `cval` as in `ndimage_warp`.  Not
   covered: `output_shape`, `output`, and 1-D (diagonal) matrices, which SciPy
   sends down its separate zoom-and-shift route; they raise NotImplementedError.
+  `image` may be resident (a CUDA tensor or a DeviceArray) and `device_output`
+  chooses a DeviceArray or a NumPy result, as in `ndimage_warp`.
   """
-  image = np.asarray(image)
+  image = _resident(image)
+  img_dtype = _np_dtype(image, 'affine_transform')
   dim = image.ndim
   if output_shape is not None or output is not None:
     raise NotImplementedError('affine_transform: output_shape and output')
@@ -452,7 +565,7 @@ def affine_transform(image: np.ndarray, matrix, offset=0.0, order=1, mode='const
       expected = [0.0] * dim + [1.0]
       if not np.all(matrix[dim] == expected):
         raise ValueError(f'Expected homogeneous transformation matrix with shape '
-                         f'{matrix.shape} for image shape {image.shape}, but bottom row was '
+                         f'{matrix.shape} for image shape {tuple(image.shape)}, but bottom row was '
                          f'not equal to {expected}')
     offset = matrix[:dim, dim]
     matrix = matrix[:dim, :dim]
@@ -463,15 +576,17 @@ def affine_transform(image: np.ndarray, matrix, offset=0.0, order=1, mode='const
     offset = np.full(dim, float(offset))
   if offset.shape != (dim,):
     raise RuntimeError('offset shape not correct')
-  if image.dtype == np.uint64:
+  if img_dtype == np.uint64:
     raise NotImplementedError('affine_transform: uint64 label volumes')
   _spline.check_order(order, 'affine_transform')
-  mode_id, cval = _boundary('affine_transform', mode, cval, order, image.dtype)
-  dtype, view = _image_dtype(image, 'affine_transform')
+  mode_id, cval = _boundary('affine_transform', mode, cval, order, img_dtype)
+  dtype, view = _image_dtype(img_dtype, 'affine_transform')
+  if device_output is None:
+    device_output = isinstance(image, torch.Tensor)
 
   dev = _dev.device()
-  img_t = torch.from_numpy(np.ascontiguousarray(image).view(view)).to(dev)
-  out_t = torch.empty(image.shape, dtype=img_t.dtype, device=dev)
+  img_t = _image_tensor(image, view, dev)
+  out_t = torch.empty(tuple(image.shape), dtype=img_t.dtype, device=dev)
   shape = (1,) * (3 - dim) + tuple(image.shape)
   full = np.zeros((3, 3), np.float64)
   full[3 - dim:, 3 - dim:] = matrix
@@ -492,10 +607,7 @@ def affine_transform(image: np.ndarray, matrix, offset=0.0, order=1, mode='const
         [(img_t.data_ptr(), shape, (shape[1] * shape[2], shape[2], 1))], dtype, order, dev)
     d.image = coeffs.data_ptr()
   _abi.check(_abi.load().sfm_affine_warp(C.byref(d)))
-  warped = out_t.cpu().numpy()
-  if image.dtype == np.uint16:
-    warped = warped.view(np.uint16)
-  return warped.astype(image.dtype)
+  return _warped(out_t, img_dtype, device_output)
 
 
 _POINT_DTYPES = {np.dtype(np.float32): _abi.POINT_F32, np.dtype(np.float64): _abi.POINT_F64,

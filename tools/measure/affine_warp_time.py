@@ -1,5 +1,5 @@
-"""Device time of an affine resample by two routes: the fused `warp.affine_transform`
-and the coordinate-map route that existed before it.
+"""Device time of an affine resample by three routes: the fused `warp.affine_transform`,
+the coordinate-map route that existed before it, and that route on resident data.
 
 One 512 x 512 x 128 uint8 volume (z, y, x = 128, 512, 512), a rotation with shear and
 anisotropic scale about a point near the centre, at order 1 and order 3:
@@ -8,19 +8,27 @@ anisotropic scale about a point near the centre, at order 1 and order 3:
           coordinates from the matrix and reads no map
   map     map_utils.make_affine_map at stride 1 (a [3, z, y, x] float64 map, 24 bytes per
           voxel) and warp.ndimage_warp of it, which is `implementation='sofima'` of
-          decorators_warp.warp_affine: the launches of sfm_affine_map and of
-          sfm_ndimage_warp / sfm_ndimage_warp_spline
+          decorators_warp.warp_affine with NumPy in and out: the launches of
+          sfm_affine_map and of sfm_ndimage_warp_rel (the map is downloaded and
+          uploaded again, relative and in its own dtype)
+  map_device  the same two functions on resident data: the DeviceArray of
+          make_affine_map goes straight to ndimage_warp, with the image a CUDA tensor
+          and device_output=True; nothing crosses to the host
 
 Per route two figures.  `kernels_ms`: the launches named above, by HIP events
 (torch.cuda.Event) recorded around them inside the call; for `map` the sum of its two
 launches.  The order-3 prefilter is the same work on both routes and is reported on its
-own.  `call_ms`: the whole call as a caller sees it, NumPy in and NumPy out, wall clock
-(the map route moves the map to the host and back, as warp_affine composes it from the
-two public functions).  2 warm-up calls, `--reps` timed ones, the routes and orders
-alternating in one process; the median and the spread (max - min) are reported.  The two
-routes must agree: make_affine_map is a few ulp off the fused coordinates (map_utils), so
-the share of differing voxels is reported and asserted to be below 1e-3.
-One JSON line per order goes to profiles/affine_warp_time.txt.
+own.  `call_ms`: the whole call as a caller sees it, wall clock with a synchronisation at
+the end: NumPy in and NumPy out for `fused` and `map` (the map route moves the map to the
+host and back), resident in and out for `map_device`.  2 warm-up calls, `--reps` timed
+ones, the routes and orders alternating in one process; the median and the spread
+(max - min) are reported.  The routes must agree: make_affine_map is a few ulp off the
+fused coordinates (map_utils), so the share of differing voxels is reported and asserted
+to be below 1e-3; `map_device` must equal `map` voxel for voxel.
+profiles/affine_warp_time.txt is rewritten: its first two lines, the record from before
+ndimage_warp read relative maps (when `map` prepared a float64 absolute map on the host,
+and there was no `map_device`), are kept as a fixed header, and one JSON line per order
+of this run follows them, so the file always has four lines.
 
   python tools/measure/affine_warp_time.py [--reps 5] [--out FILE]
 """
@@ -44,7 +52,7 @@ VOLUME = (128, 512, 512)      # z, y, x
 class Events:
   """HIP events around the named library calls (and _spline.prefilter) of a call."""
 
-  NAMES = ('sfm_affine_warp', 'sfm_affine_map', 'sfm_ndimage_warp', 'sfm_ndimage_warp_spline')
+  NAMES = ('sfm_affine_warp', 'sfm_affine_map', 'sfm_ndimage_warp_rel')
 
   def __init__(self):
     self._lib = _abi.load()
@@ -104,13 +112,23 @@ def fused(img, m_zyx, order):
   return warp.affine_transform(img, m_zyx, order=order)
 
 
-def by_map(img, m_zyx, order):
+def affine_map(shape, m_zyx):
   # make_affine_map takes xyz rows and columns; the map's channels are x, y, z
   m_xyz = np.concatenate([m_zyx[::-1, :3][:, ::-1], m_zyx[::-1, 3:]], axis=1)
-  box = types.SimpleNamespace(start=np.zeros(3, np.int64), size=np.array(img.shape[::-1]))
-  cmap = map_utils.make_affine_map(m_xyz, box, [1, 1, 1])
+  box = types.SimpleNamespace(start=np.zeros(3, np.int64), size=np.array(shape[::-1]))
+  return map_utils.make_affine_map(m_xyz, box, [1, 1, 1])
+
+
+def by_map(img, m_zyx, order):
+  cmap = affine_map(img.shape, m_zyx)
   return warp.ndimage_warp(img, np.asarray(cmap), [1, 1, 1], img.shape[::-1], [0, 0, 0],
                            order=order)
+
+
+def by_map_device(img_t, m_zyx, order):
+  shape = tuple(img_t.shape)
+  return warp.ndimage_warp(img_t, affine_map(shape, m_zyx), [1, 1, 1], shape[::-1], [0, 0, 0],
+                           order=order, device_output=True)
 
 
 def wall(fn):
@@ -130,15 +148,18 @@ def main():
   rng = np.random.default_rng(0)
   img = rng.integers(0, 256, VOLUME).astype(np.uint8)
   m = inverse_matrix()
-  routes = {'fused': fused, 'map': by_map}
+  img_t = torch.from_numpy(img).to('cuda')      # the resident image of map_device
+  routes = {'fused': fused, 'map': by_map, 'map_device': by_map_device}
   kernels = {'fused': ('sfm_affine_warp',),
-             'map': ('sfm_affine_map', 'sfm_ndimage_warp', 'sfm_ndimage_warp_spline')}
+             'map': ('sfm_affine_map', 'sfm_ndimage_warp_rel'),
+             'map_device': ('sfm_affine_map', 'sfm_ndimage_warp_rel')}
 
   differ = {}
   for order in (1, 3, 1, 3):             # (two warm-up calls of either route and order)
     a, b = fused(img, m, order), by_map(img, m, order)
     differ[order] = float(np.mean(a != b))
     assert np.mean(a != 0) > 0.9 and differ[order] < 1e-3, differ
+    assert np.array_equal(np.asarray(by_map_device(img_t, m, order)), b)
   del a, b
 
   times = {(r, o): {'call': [], 'kernels': [], 'prefilter': []} for r in routes for o in (1, 3)}
@@ -146,7 +167,7 @@ def main():
     for _ in range(args.reps):
       for order in (1, 3):
         for name, fn in routes.items():
-          ms, _ = wall(lambda: fn(img, m, order))
+          ms, _ = wall(lambda: fn(img_t if name == 'map_device' else img, m, order))
           parts = ev.take()
           rec = times[name, order]
           rec['call'].append(ms)
@@ -164,9 +185,15 @@ def main():
           continue
         line[f'{name}_{key}_ms'], line[f'{name}_{key}_spread_ms'] = stats(rec[key])
     line['map_over_fused_kernels'] = round(line['map_kernels_ms'] / line['fused_kernels_ms'], 2)
+    line['map_over_map_device_call'] = round(line['map_call_ms'] / line['map_device_call_ms'], 1)
     line['fused_Gvoxel_s'] = round(voxels / line['fused_kernels_ms'] / 1e6, 2)
     lines.append(json.dumps(line))
     print(lines[-1], flush=True)
+  header = []      # the two lines of the earlier record: those without a map_device route
+  if os.path.exists(args.out):
+    with open(args.out) as f:
+      header = [ln.strip() for ln in f if ln.strip() and 'map_device_call_ms' not in ln][:2]
+  lines = header + lines
   with open(args.out, 'w') as f:
     f.write('\n'.join(lines) + '\n')
 
