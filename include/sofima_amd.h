@@ -46,7 +46,11 @@ extern "C" {
                                    sfm_ndimage_warp_spline and
                                    sfm_render_tiles3d_spline, and
                                    sfm_ndimage_warp_mode and sfm_affine_warp, and
-                                   sfm_ndimage_warp_rel */
+                                   sfm_ndimage_warp_rel, and
+                                   sfm_spline_prefilter_mode and sfm_spline_mode_pad
+                                   (with them the switch SFM_SPLINE_MODES, under
+                                   which the mode entry points read padded
+                                   coefficients for two modes; off: unchanged) */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -106,6 +110,9 @@ int sfm_device_count(int* count);
  *   SFM_MFMA_GUARD_2R=1   lazy / pruned path: the row band around hot rows and pruned tiles
  *                         is 2 x peak_radius rows everywhere (default: the rows the peak
  *                         kernels can read -- the clamped window and min_distance)
+ *   SFM_SPLINE_MODES=1    (not a same-result switch: it adds a capability) spline orders
+ *                         2 .. 5 take the boundary modes nearest, reflect, grid-constant and
+ *                         grid-wrap (sfm_spline_prefilter_mode; default: rejected)
  *   SFM_MASKED_FAST=0     masked patches always take all eight passes
  *   SFM_MASKED_DEADROWS=0 no overlap-rule skips in the masked assembly
  *   SFM_MASKED_GROUPS=n   masked matrix-core path: reference batches (`group` patches each)
@@ -777,7 +784,8 @@ int sfm_render_tiles3d_spline(const SfmRenderTilesDesc* desc, const double* coef
  * SciPy's behaviour in tests/ndwarp_modes_ref.py, which a CPU test pins to SciPy
  * bit for bit.  Orders 0 and 1 take every mode; orders 2 .. 5 take CONSTANT,
  * MIRROR and WRAP, whose B-spline coefficients are those of
- * sfm_spline_prefilter (the others need another prefilter and are rejected).
+ * sfm_spline_prefilter; the others need another prefilter and are rejected,
+ * unless the switch SFM_SPLINE_MODES is on: see sfm_spline_prefilter_mode below.
  * An integer image takes cval through the conversion of a sampled value and
  * needs a finite one.  A NaN coordinate, or one of magnitude 2^31 and above,
  * gives cval under every mode (SciPy casts it to an integer there, which is
@@ -864,6 +872,48 @@ typedef struct SfmNdWarpRelDesc {
 } SfmNdWarpRelDesc;
 
 int sfm_ndimage_warp_rel(const SfmNdWarpRelDesc* desc);
+
+/* ------------------------------------------------------------------------
+ * Orders 2 .. 5 under SciPy's remaining boundary modes: NEAREST, REFLECT
+ * ("grid-mirror"), GRID_CONSTANT and GRID_WRAP.  Opt-in: the switch
+ * SFM_SPLINE_MODES=1 (sfm_set_option, or the environment variable as the
+ * default); without it every call below and above rejects these modes at these
+ * orders as before.  The switch lifts the mode restriction only; callers that
+ * gate the orders themselves (the Python layer: SFM_SPLINE_ORDERS) still do.
+ *
+ * scipy.ndimage.spline_filter initialises its recursion in one of three ways:
+ * mirror for MIRROR, CONSTANT, GRID_CONSTANT and WRAP (sfm_spline_prefilter),
+ * reflect for REFLECT and NEAREST, wrap for GRID_WRAP alone.  And
+ * map_coordinates / affine_transform pad the image by 12 samples on every axis
+ * the array has before they filter for NEAREST (edge values) and GRID_CONSTANT
+ * (cval, cast to the image's type), and sample the padded coefficients at
+ * coordinate + 12 under the same mode.  sfm_spline_mode_pad returns that pad for
+ * a mode: 12 or 0 (-1: no such mode).
+ *
+ * sfm_spline_prefilter_mode is sfm_spline_prefilter with the initialisation and
+ * the pad of `mode`.  `ndim` is the real dimensionality of every item (2:
+ * shape[0] = 1, and that axis is not padded; a real axis of length 1 IS padded
+ * and filtered).  With a pad p the coefficients of an item are dense in
+ * shape + 2p on its real axes -- coeff_offset and coeffs_len count those -- while
+ * `shape` and `pitch` stay those of the source region, which is read through a
+ * clamped index (NEAREST), or replaced by `pad_value` outside it (GRID_CONSTANT;
+ * the value as the image's type holds it, the caller converts; ignored by the
+ * other modes): no padded copy of the image exists.  SfmSplineItem.zn holds, per
+ * axis k of the coefficients' length n and pole p, pow(pole, n - 1) for the
+ * mirror initialisation and pow(pole, n) for the reflect one; the wrap one
+ * reads none.  CONSTANT, MIRROR and WRAP are sfm_spline_prefilter itself.
+ *
+ * With the switch on, sfm_ndimage_warp_mode, sfm_ndimage_warp_rel (has_boundary)
+ * and sfm_affine_warp accept the four modes at orders 2 .. 5.  `image` then
+ * holds the coefficients of sfm_spline_prefilter_mode for the same mode and
+ * ndim; image_shape / shape stays the shape of the image itself: for NEAREST and
+ * GRID_CONSTANT the library adds the 12 to the image-step coordinate, in double
+ * (after the offset in sfm_affine_warp; the map step of sfm_ndimage_warp is order
+ * 1 and unpadded), and samples with the padded shape.
+ * ---------------------------------------------------------------------- */
+int sfm_spline_mode_pad(int32_t mode);
+int sfm_spline_prefilter_mode(const SfmSplinePrefilterDesc* desc, int32_t mode, int32_t ndim,
+                              double pad_value);
 
 /* ------------------------------------------------------------------------
  * Map geometry: the one-pass helpers that the reference's renderers call

@@ -677,6 +677,9 @@ SIGNATURES = {
     'sfm_ndimage_warp_mode': (C.c_int, [C.POINTER(SfmNdWarpDesc), i32, C.c_double]),
     'sfm_affine_warp': (C.c_int, [C.POINTER(SfmAffineWarpDesc)]),
     'sfm_ndimage_warp_rel': (C.c_int, [C.POINTER(SfmNdWarpRelDesc)]),
+    'sfm_spline_mode_pad': (C.c_int, [i32]),
+    'sfm_spline_prefilter_mode': (C.c_int, [C.POINTER(SfmSplinePrefilterDesc), i32, i32,
+                                            C.c_double]),
     'sfm_map_shift': (C.c_int, [C.POINTER(SfmMapShiftDesc)]),
     'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
     'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),

@@ -61,6 +61,13 @@ inline int measure_option_int(const char* name, int dflt) {
   return value_int(measure_option(name), dflt);
 }
 
+// SFM_SPLINE_MODES: spline orders 2 .. 5 take SciPy's boundary modes beyond
+// constant, mirror and wrap (off unless set to something other than "" and "0").
+inline bool spline_modes_enabled() {
+  const char* e = option("SFM_SPLINE_MODES");
+  return e && e[0] && !(e[0] == '0' && !e[1]);
+}
+
 // Compute units of the current device (hipGetDevice), looked up once per device;
 // 256 when the query fails.
 int device_cus();

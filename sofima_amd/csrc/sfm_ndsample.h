@@ -32,6 +32,10 @@ enum : int {
 struct Boundary {
   int mode = kModeConstant;
   double cval = 0.0;
+  // Orders 2 .. 5 under "nearest" and "grid-constant": the coefficients are those of
+  // the image padded by `pad` samples per axis (sfm_spline_prefilter_mode), and the
+  // kernels add it to the image-step coordinate; 0 everywhere else.
+  int pad = 0;
 };
 
 // The coordinate `c` on an axis of length `len`, folded by the mode.  false: the
@@ -267,7 +271,16 @@ __device__ __forceinline__ void spline_weights<5>(double x, double* w) {
 //
 // MODES: "constant" with a fill value, "mirror" and "wrap", the modes whose
 // coefficients are these; only the coordinate is folded, the taps mirror as above.
-template <int DIM, int ORDER, bool MODES = false, typename A>
+//
+// TAPS (with MODES): the other modes.  Every tap is folded by fold_tap, as in
+// linear_sample: "nearest" clamps, "reflect" and "grid-wrap" fold with their
+// periods, and a tap that "grid-constant" finds outside the array is cval (its
+// offset is kept as -1: offsets inside the array are never negative).  The
+// coefficients are those of the mode's own prefilter, for "nearest" and
+// "grid-constant" of the padded image (sfm_spline_prefilter_mode): `shape` is then
+// the padded shape and `c` is shifted.  An instantiation of its own, so that the
+// three modes above keep their registers.
+template <int DIM, int ORDER, bool MODES = false, bool TAPS = false, typename A>
 __device__ __forceinline__ double spline_sample(const A a, const int* shape, const double* c,
                                                 const long long* pitch = nullptr,
                                                 const Boundary b = Boundary()) {
@@ -297,6 +310,12 @@ __device__ __forceinline__ double spline_sample(const A a, const int* shape, con
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       long long i = start + k;
+      if constexpr (TAPS) {
+        bool fill;
+        i = fold_tap(b.mode, len, i, fill);
+        off[d][k] = fill ? -1 : i * step[d];
+        continue;
+      }
       if (len == 1) {
         i = 0;
       } else {
@@ -313,7 +332,12 @@ __device__ __forceinline__ double spline_sample(const A a, const int* shape, con
     for (int k0 = 0; k0 < K; ++k0) {
 #pragma unroll
       for (int k1 = 0; k1 < K; ++k1) {
-        double coeff = static_cast<double>(a[off[0][k0] + off[1][k1]]);
+        double coeff;
+        if constexpr (TAPS)
+          coeff = (off[0][k0] | off[1][k1]) < 0 ? b.cval
+                                                : static_cast<double>(a[off[0][k0] + off[1][k1]]);
+        else
+          coeff = static_cast<double>(a[off[0][k0] + off[1][k1]]);
         coeff = coeff * w[0][k0];
         coeff = coeff * w[1][k1];
         acc = acc + coeff;
@@ -327,7 +351,13 @@ __device__ __forceinline__ double spline_sample(const A a, const int* shape, con
       for (int k1 = 0; k1 < K; ++k1) {
 #pragma unroll
         for (int k2 = 0; k2 < K; ++k2) {
-          double coeff = static_cast<double>(a[off[0][k0] + off[1][k1] + off[2][k2]]);
+          double coeff;
+          if constexpr (TAPS)
+            coeff = (off[0][k0] | off[1][k1] | off[2][k2]) < 0
+                        ? b.cval
+                        : static_cast<double>(a[off[0][k0] + off[1][k1] + off[2][k2]]);
+          else
+            coeff = static_cast<double>(a[off[0][k0] + off[1][k1] + off[2][k2]]);
           coeff = coeff * w[0][k0];
           coeff = coeff * w[1][k1];
           coeff = coeff * w[2][k2];

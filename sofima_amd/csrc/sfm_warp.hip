@@ -271,7 +271,10 @@ __global__ void __launch_bounds__(kBlock) ndimage_warp_kernel(NdWarpArgs<MAP> a)
 // the node grid the dense coordinate is cval (in source voxels) or the folded
 // node value, and the image sample follows the same rule; an integer image takes
 // cval through nd_convert like a sampled value.
-template <int DIM, typename T, int ORDER, typename MAP>
+//
+// TAPS: orders 2 .. 5 under the modes beyond "constant", "mirror" and "wrap"
+// (spline_sample<.., TAPS>): kernels of their own, which the three modes never run.
+template <int DIM, typename T, int ORDER, typename MAP, bool TAPS = false>
 __global__ void __launch_bounds__(kBlock)
 ndimage_warp_mode_kernel(NdWarpArgs<MAP> a, sfm::Boundary b) {
   const long long n = (long long)a.oshape[0] * a.oshape[1] * a.oshape[2];
@@ -295,8 +298,18 @@ ndimage_warp_mode_kernel(NdWarpArgs<MAP> a, sfm::Boundary b) {
                                              a.mshape, pos, nullptr, b);
   double v;
   if constexpr (ORDER >= 2) {
-    v = sfm::spline_sample<DIM, ORDER, true>(static_cast<const double*>(a.image), a.ishape,
-                                             dense, nullptr, b);
+    if constexpr (TAPS) {
+      // "nearest" / "grid-constant": a.image holds the coefficients of the padded image
+      // and a.ishape its shape; the map step above is order 1 and unpadded
+      if (b.pad) {
+#pragma unroll
+        for (int d = 0; d < DIM; ++d)     // (the magnitude limit is that of the caller's coordinate)
+        dense[d] = fabs(dense[d]) < 2147483648.0 ? dense[d] + static_cast<double>(b.pad)
+                                                 : static_cast<double>(NAN);
+      }
+    }
+    v = sfm::spline_sample<DIM, ORDER, true, TAPS>(static_cast<const double*>(a.image),
+                                                   a.ishape, dense, nullptr, b);
   } else {
     const T* img = static_cast<const T*>(a.image);
     v = a.order == 0 ? sfm::nearest_sample<DIM, true>(img, a.ishape, dense, nullptr, b)
@@ -307,19 +320,36 @@ ndimage_warp_mode_kernel(NdWarpArgs<MAP> a, sfm::Boundary b) {
 }
 
 // What the samplers take: a mode of the list; orders 2 .. 5 only the modes whose
-// coefficients sfm_spline_prefilter computes; a finite fill value for integers
-// (the conversion of NaN or an infinity to an integer is undefined).
+// coefficients sfm_spline_prefilter computes, and with the switch SFM_SPLINE_MODES
+// the others, on the coefficients of sfm_spline_prefilter_mode; a finite fill value
+// for integers (the conversion of NaN or an infinity to an integer is undefined).
 int check_boundary(const char* what, int mode, double cval, int order, int dtype) {
   if (mode < 0 || mode >= sfm::kModeCount)
     return sfm::fail(SFM_ERR_INVALID, "%s: boundary mode %d", what, mode);
   if (order >= 2 && mode != sfm::kModeConstant && mode != sfm::kModeMirror &&
-      mode != sfm::kModeWrap)
+      mode != sfm::kModeWrap && !sfm::spline_modes_enabled())
     return sfm::fail(SFM_ERR_INVALID,
-                     "%s: boundary mode %d at order %d (constant, mirror and wrap are built)",
+                     "%s: boundary mode %d at order %d (constant, mirror and wrap are built; "
+                     "the others need the switch SFM_SPLINE_MODES=1)",
                      what, mode, order);
   if (dtype != SFM_DTYPE_F32 && !std::isfinite(cval))
     return sfm::fail(SFM_ERR_INVALID, "%s: non-finite cval for an integer image", what);
   return SFM_OK;
+}
+
+// orders 2 .. 5: the modes whose taps do not mirror (the TAPS kernels)
+bool spline_taps(int mode) {
+  return mode != sfm::kModeConstant && mode != sfm::kModeMirror && mode != sfm::kModeWrap;
+}
+
+// The Boundary of a checked mode: orders 2 .. 5 under "nearest" and "grid-constant"
+// read the coefficients of the padded image.
+sfm::Boundary make_boundary(int mode, double cval, int order) {
+  sfm::Boundary b;
+  b.mode = mode;
+  b.cval = cval;
+  b.pad = order >= 2 ? sfm_spline_mode_pad(mode) : 0;
+  return b;
 }
 
 }  // namespace
@@ -360,6 +390,11 @@ int ndimage_warp_launch(const D* d, const MAP& map, bool spline,
     if (k >= 3 - d->ndim && !(d->stride[k] != 0.0))
       return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: stride");
     a.ishape[k] = d->image_shape[k];
+    if (bnd && bnd->pad && k >= 3 - d->ndim) {
+      if (d->image_shape[k] > 0x7fffffff - 2 * bnd->pad)
+        return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: bad shape");
+      a.ishape[k] += 2 * bnd->pad;
+    }
     a.mshape[k] = d->map_shape[k];
     a.oshape[k] = d->out_shape[k];
     a.stride[k] = d->stride[k];
@@ -370,9 +405,16 @@ int ndimage_warp_launch(const D* d, const MAP& map, bool spline,
   if (grid > 0x7fffffffLL) return sfm::fail(SFM_ERR_INVALID, "ndimage_warp: too large");
   hipStream_t st = static_cast<hipStream_t>(d->stream);
   const dim3 g(static_cast<unsigned>(grid)), b(kBlock);
+  const bool taps = bnd && spline && spline_taps(bnd->mode);
 #define SFM_NDW_ORDER(T, ORDER)                                                    \
   do {                                                                             \
-    if (bnd && d->ndim == 2)                                                       \
+    if (taps && d->ndim == 2)                                                      \
+      hipLaunchKernelGGL((ndimage_warp_mode_kernel<2, T, ORDER, MAP, (ORDER >= 2)>), g, b, 0, \
+                         st, a, *bnd);                                             \
+    else if (taps)                                                                 \
+      hipLaunchKernelGGL((ndimage_warp_mode_kernel<3, T, ORDER, MAP, (ORDER >= 2)>), g, b, 0, \
+                         st, a, *bnd);                                             \
+    else if (bnd && d->ndim == 2)                                                  \
       hipLaunchKernelGGL((ndimage_warp_mode_kernel<2, T, ORDER, MAP>), g, b, 0, st, a, *bnd); \
     else if (bnd)                                                                  \
       hipLaunchKernelGGL((ndimage_warp_mode_kernel<3, T, ORDER, MAP>), g, b, 0, st, a, *bnd); \
@@ -419,9 +461,7 @@ extern "C" int sfm_ndimage_warp_mode(const SfmNdWarpDesc* d, int32_t mode, doubl
     return sfm::fail(SFM_ERR_INVALID, "ndimage_warp_mode: interpolation order %d (0 .. 5)",
                      d->order);
   if (int rc = check_boundary("ndimage_warp_mode", mode, cval, d->order, d->dtype)) return rc;
-  sfm::Boundary b;
-  b.mode = mode;
-  b.cval = cval;
+  const sfm::Boundary b = make_boundary(mode, cval, d->order);
   return ndimage_warp_launch(d, AbsoluteMap{d->src_map}, d->order >= 2, &b);
 }
 
@@ -450,8 +490,7 @@ extern "C" int sfm_ndimage_warp_rel(const SfmNdWarpRelDesc* d) {
   if (d->has_boundary) {
     if (int rc = check_boundary("ndimage_warp_rel", d->mode, d->cval, d->order, d->dtype))
       return rc;
-    b.mode = d->mode;
-    b.cval = d->cval;
+    b = make_boundary(d->mode, d->cval, d->order);
   }
   const sfm::Boundary* bnd = d->has_boundary ? &b : nullptr;
   return d->map_f64 ? ndimage_warp_rel_launch<double>(d, bnd)
@@ -472,12 +511,13 @@ struct AffineArgs {
   const void* image;
   void* out;
   int order;
-  int shape[3];
+  int shape[3];     // of out
+  int ishape[3];    // of what is sampled: shape, or with b.pad the padded coefficients
   double m[3][3], off[3];
   sfm::Boundary b;
 };
 
-template <int DIM, typename T, int ORDER = 0>
+template <int DIM, typename T, int ORDER = 0, bool TAPS = false>
 __global__ void __launch_bounds__(kBlock) affine_warp_kernel(AffineArgs a) {
   const long long n = (long long)a.shape[0] * a.shape[1] * a.shape[2];
   const long long i = blockIdx.x * (long long)kBlock + threadIdx.x;
@@ -497,12 +537,20 @@ __global__ void __launch_bounds__(kBlock) affine_warp_kernel(AffineArgs a) {
   }
   double v;
   if constexpr (ORDER >= 2) {
-    v = sfm::spline_sample<DIM, ORDER, true>(static_cast<const double*>(a.image), a.shape, c,
-                                             nullptr, a.b);
+    if constexpr (TAPS) {
+      if (a.b.pad) {                     // after the offset, as SciPy adds it
+#pragma unroll
+        for (int h = 0; h < DIM; ++h)     // (the magnitude limit is that of the unshifted coordinate)
+        c[h] = fabs(c[h]) < 2147483648.0 ? c[h] + static_cast<double>(a.b.pad)
+                                         : static_cast<double>(NAN);
+      }
+    }
+    v = sfm::spline_sample<DIM, ORDER, true, TAPS>(static_cast<const double*>(a.image), a.ishape,
+                                                   c, nullptr, a.b);
   } else {
     const T* img = static_cast<const T*>(a.image);
-    v = a.order == 0 ? sfm::nearest_sample<DIM, true>(img, a.shape, c, nullptr, a.b)
-                     : sfm::linear_sample<DIM, true>(img, a.shape, c, nullptr, a.b);
+    v = a.order == 0 ? sfm::nearest_sample<DIM, true>(img, a.ishape, c, nullptr, a.b)
+                     : sfm::linear_sample<DIM, true>(img, a.ishape, c, nullptr, a.b);
   }
   constexpr double vmax = sizeof(T) == 1 ? 255.0 : 65535.0;
   static_cast<T*>(a.out)[i] = sfm::nd_convert<T>(v, vmax);
@@ -520,14 +568,18 @@ extern "C" int sfm_affine_warp(const SfmAffineWarpDesc* d) {
   a.image = d->image;
   a.out = d->out;
   a.order = d->order;
-  a.b.mode = d->mode;
-  a.b.cval = d->cval;
+  a.b = make_boundary(d->mode, d->cval, d->order);
   long long n = 1;
   for (int k = 0; k < 3; ++k) {
     if (d->shape[k] < 1) return sfm::fail(SFM_ERR_INVALID, "affine_warp: bad shape");
     if (d->ndim == 2 && k == 0 && d->shape[0] != 1)
       return sfm::fail(SFM_ERR_INVALID, "affine_warp: 2-d arrays have shape[0] = 1");
-    a.shape[k] = d->shape[k];
+    a.shape[k] = a.ishape[k] = d->shape[k];
+    if (a.b.pad && k >= 3 - d->ndim) {
+      if (d->shape[k] > 0x7fffffff - 2 * a.b.pad)
+        return sfm::fail(SFM_ERR_INVALID, "affine_warp: bad shape");
+      a.ishape[k] += 2 * a.b.pad;
+    }
     a.off[k] = d->offset[k];
     for (int j = 0; j < 3; ++j) a.m[k][j] = d->matrix[3 * k + j];
     n *= d->shape[k];
@@ -536,9 +588,14 @@ extern "C" int sfm_affine_warp(const SfmAffineWarpDesc* d) {
   if (grid > 0x7fffffffLL) return sfm::fail(SFM_ERR_INVALID, "affine_warp: too large");
   hipStream_t st = static_cast<hipStream_t>(d->stream);
   const dim3 g(static_cast<unsigned>(grid)), b(kBlock);
+  const bool taps = d->order >= 2 && spline_taps(d->mode);
 #define SFM_AFF_ORDER(T, ORDER)                                                    \
   do {                                                                             \
-    if (d->ndim == 2)                                                              \
+    if (taps && d->ndim == 2)                                                      \
+      hipLaunchKernelGGL((affine_warp_kernel<2, T, ORDER, (ORDER >= 2)>), g, b, 0, st, a); \
+    else if (taps)                                                                 \
+      hipLaunchKernelGGL((affine_warp_kernel<3, T, ORDER, (ORDER >= 2)>), g, b, 0, st, a); \
+    else if (d->ndim == 2)                                                         \
       hipLaunchKernelGGL((affine_warp_kernel<2, T, ORDER>), g, b, 0, st, a);       \
     else                                                                           \
       hipLaunchKernelGGL((affine_warp_kernel<3, T, ORDER>), g, b, 0, st, a);       \

@@ -122,7 +122,9 @@ def warp_coord_map(img_xyz, coord_map, mode: str = 'constant',
 
   coord_map: [3, z, y, x] relative map; `mode` / `cval`: SciPy's boundary mode
   and fill value, applied to the map interpolation and to the image sample
-  alike (see `warp.ndimage_warp`); scale_xyz: factors for the map's channels;
+  alike (see `warp.ndimage_warp`: orders 2 to 5 take 'constant', 'mirror' and
+  'wrap', and the other modes with the switch SFM_SPLINE_MODES=1); scale_xyz:
+  factors for the map's channels;
   `warp_args` (stride, overlap, order, boxes ...) go to `warp.ndimage_warp`,
   `work_size` defaults to the image shape.  Image and map may be resident (CUDA
   tensors or DeviceArrays): the `scale_xyz` product and the transposes then run on

@@ -275,10 +275,7 @@ def _boundary(what: str, mode, cval, order, dtype) -> tuple[int, float]:
   """(SFM_MODE_*, cval) of SciPy's `mode` / `cval`, or the error of what is not built."""
   if mode not in _abi.MODES:
     raise ValueError(f'{what}: boundary mode {mode!r} (one of {sorted(_abi.MODES)})')
-  if order in _spline.ORDERS and mode not in ('constant', 'mirror', 'wrap'):
-    raise NotImplementedError(
-        f'{what}: boundary mode {mode!r} at interpolation order {order} (orders 2 to 5 take '
-        "'constant', 'mirror' and 'wrap'; the other modes need another B-spline prefilter)")
+  _spline.check_mode(mode, order, what)
   cval = float(cval)
   if np.dtype(dtype).kind != 'f' and not np.isfinite(cval):
     raise ValueError(f'{what}: cval {cval} for a {np.dtype(dtype)} image')
@@ -382,7 +379,11 @@ def ndimage_warp(image, coord_map, stride, work_size, overlap,
   reference passes the callable to both -- outside the node grid the dense
   coordinate is `cval` in source voxels (or the folded node value), and the
   image sample follows the same rule.  Orders 0 and 1 take every mode of SciPy,
-  orders 2 to 5 'constant', 'mirror' and 'wrap'; an integer image needs a
+  orders 2 to 5 'constant', 'mirror' and 'wrap', and with the switch
+  SFM_SPLINE_MODES=1 the others too: 'nearest', 'reflect' ('grid-mirror'),
+  'grid-constant' and 'grid-wrap' have B-spline prefilters of their own, and
+  'nearest' and 'grid-constant' filter the image padded by 12 samples per axis, as
+  SciPy does (the workspace is then 8 bytes per padded voxel); an integer image needs a
   finite `cval` and takes it through the conversion of a sampled value.  A NaN
   coordinate or one of magnitude 2**31 and above gives `cval` (SciPy's result
   there is an undefined cast, except under 'constant').
@@ -411,7 +412,9 @@ def ndimage_warp(image, coord_map, stride, work_size, overlap,
   if img_dtype == np.uint64:
     raise NotImplementedError('ndimage_warp: uint64 label volumes (use warp_subvolume)')
   _spline.check_order(order, 'ndimage_warp')
+  mode = 'constant'
   if boundary is not None:
+    mode = boundary[0]
     boundary = _boundary('ndimage_warp', boundary[0], boundary[1], order, img_dtype)
   if dim not in (2, 3):
     raise ValueError(f'ndimage_warp: {dim}-d data')
@@ -478,7 +481,8 @@ def ndimage_warp(image, coord_map, stride, work_size, overlap,
   if order in _spline.ORDERS:
     ishape = pad + tuple(image.shape)
     coeffs, _ = _spline.prefilter(
-        [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev)
+        [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev,
+        mode, dim, _spline.pad_value(boundary[1], img_dtype) if boundary else 0.0)
     d.image = coeffs.data_ptr()
   lib = _abi.load()
   if relative:
@@ -604,7 +608,8 @@ def affine_transform(image, matrix, offset=0.0, order=1, mode='constant', cval=0
   d.stream = _dev.stream_ptr()
   if order in _spline.ORDERS:
     coeffs, _ = _spline.prefilter(
-        [(img_t.data_ptr(), shape, (shape[1] * shape[2], shape[2], 1))], dtype, order, dev)
+        [(img_t.data_ptr(), shape, (shape[1] * shape[2], shape[2], 1))], dtype, order, dev,
+        mode, dim, _spline.pad_value(cval, img_dtype))
     d.image = coeffs.data_ptr()
   _abi.check(_abi.load().sfm_affine_warp(C.byref(d)))
   return _warped(out_t, img_dtype, device_output)
