@@ -50,7 +50,9 @@ extern "C" {
                                    sfm_spline_prefilter_mode and sfm_spline_mode_pad
                                    (with them the switch SFM_SPLINE_MODES, under
                                    which the mode entry points read padded
-                                   coefficients for two modes; off: unchanged) */
+                                   coefficients for two modes; off: unchanged),
+                                   and sfm_fill_missing_nearest with
+                                   sfm_fill_missing_nearest_workspace_bytes */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -1018,6 +1020,43 @@ typedef struct SfmWarpPointsDesc {
 } SfmWarpPointsDesc;
 
 int sfm_warp_points(const SfmWarpPointsDesc* desc);
+
+/* map_utils.fill_missing (map_utils.py:227-304), the branch without Delaunay
+ * interpolation (interpolate_first=False).  A node is valid when all its
+ * channels are finite.  A 2-channel map is filled per z slice, a 3-channel map
+ * as one volume ("problem" below).  out is written as follows:
+ *   - the map holds no NaN: out = coord_map (inf entries stay);
+ *   - a problem without a valid node: zeros with invalid_to_zero, else NaN
+ *     (quiet, positive, zero payload) with extrapolate, else unchanged;
+ *   - otherwise, with extrapolate, every invalid node gets in all channels the
+ *     bits of the valid node at the smallest squared Euclidean distance in node
+ *     indices (isotropic; z counts for 3 channels only), the lowest C-order
+ *     index of [z, y, x] among equidistant ones; valid nodes keep their bits.
+ *     Without extrapolate the problem is copied.
+ * Distances are exact 32-bit integers: every axis holds at most
+ * SFM_FILL_MISSING_MAX_AXIS nodes and the map at most 2^31 - 1 nodes per
+ * channel (SFM_ERR_INVALID above either).  has_nan receives non-zero when the
+ * map holds a NaN.  Deterministic; coord_map is only read and must not overlap
+ * out. */
+#define SFM_FILL_MISSING_MAX_AXIS 16384
+
+typedef struct SfmFillMissingDesc {
+  int32_t ncomp;                /* 2: per z slice, 3: one volume              */
+  int32_t f64;                  /* 1: the maps hold doubles, 0: floats        */
+  int32_t shape[3];             /* z, y, x                                    */
+  int32_t invalid_to_zero;
+  int32_t extrapolate;
+  const void* coord_map;        /* device [ncomp, z, y, x]                    */
+  void* out;                    /* device, same shape and type                */
+  int32_t* has_nan;             /* device [1]                                 */
+  void* workspace;              /* sfm_fill_missing_nearest_workspace_bytes() */
+  size_t workspace_bytes;
+  void* stream;
+} SfmFillMissingDesc;
+
+/* 0 for a NULL or unacceptable descriptor (only ncomp and shape are read). */
+size_t sfm_fill_missing_nearest_workspace_bytes(const SfmFillMissingDesc* desc);
+int sfm_fill_missing_nearest(const SfmFillMissingDesc* desc);
 
 /* ------------------------------------------------------------------------
  * Dynamic-range mask of an overlap strip, the step in front of the

@@ -462,6 +462,25 @@ class SfmWarpPointsDesc(C.Structure):
   ]
 
 
+FILL_MISSING_MAX_AXIS = 16384
+
+
+class SfmFillMissingDesc(C.Structure):
+  _fields_ = [
+      ('ncomp', i32),
+      ('f64', i32),
+      ('shape', i32 * 3),
+      ('invalid_to_zero', i32),
+      ('extrapolate', i32),
+      ('coord_map', C.c_void_p),
+      ('out', C.c_void_p),
+      ('has_nan', C.c_void_p),
+      ('workspace', C.c_void_p),
+      ('workspace_bytes', C.c_size_t),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmRangeMaskDesc(C.Structure):
   _fields_ = [
       ('dtype', i32),
@@ -684,6 +703,8 @@ SIGNATURES = {
     'sfm_map_extents': (C.c_int, [C.POINTER(SfmMapExtentsDesc)]),
     'sfm_affine_map': (C.c_int, [C.POINTER(SfmAffineMapDesc)]),
     'sfm_warp_points': (C.c_int, [C.POINTER(SfmWarpPointsDesc)]),
+    'sfm_fill_missing_nearest_workspace_bytes': (C.c_size_t, [C.POINTER(SfmFillMissingDesc)]),
+    'sfm_fill_missing_nearest': (C.c_int, [C.POINTER(SfmFillMissingDesc)]),
     'sfm_range_mask': (C.c_int, [C.POINTER(SfmRangeMaskDesc), C.c_void_p]),
     'sfm_target_mesh': (C.c_int, [C.POINTER(SfmTargetMeshDesc), C.c_void_p,
                                   C.c_void_p, C.c_void_p]),

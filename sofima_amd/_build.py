@@ -42,6 +42,7 @@ SOURCES = {
     'sfm_warp.hip': ['-ffp-contract=off'],
     'sfm_spline.hip': ['-ffp-contract=off'],
     'sfm_mapgeom.hip': ['-ffp-contract=off'],
+    'sfm_fillmissing.hip': [],
 }
 # SFM_BUILD_FLAGS: extra flags for every unit (-DSFM_MEASUREMENT_SWITCHES: the library
 # honours the measurement-only switches, see csrc/sfm_common.h)

@@ -4,16 +4,20 @@ Drop-ins for `map_utils.compose_maps_fast` of the reference
 (map_utils.py:616-734), `map_utils.mask_irregular` (:737-786), the 2-D
 branch of `map_utils.invert_map` (:392-463) and the helpers that the
 reference's renderers call around them: `to_absolute` / `to_relative`
-(:150-224), `outer_box` (:307-342), `inner_box` (:345-389, maps without NaN)
-and `make_affine_map` (:789-811).  The helpers are one pass over memory each
-and take and return `DeviceArray`s, so a map produced by `invert_map` or
-`compose_maps_fast` is shifted or measured without a host round trip.
-`invert_map` triangulates the deformed positions, so its Delaunay
+(:150-224), `outer_box` (:307-342), `inner_box` (:345-389, maps without NaN),
+`make_affine_map` (:789-811) and the nearest-node branch of `fill_missing`
+(:227-304 with `interpolate_first=False`).  The helpers are one pass over
+memory each and take and return `DeviceArray`s, so a map produced by
+`invert_map` or `compose_maps_fast` is shifted or measured without a host
+round trip.  `invert_map` triangulates the deformed positions, so its Delaunay
 triangulation is unique and the device result has a parity contract.
-`resample_map`, `compose_maps` and `fill_missing` triangulate the regular
-lattice, where every quad is co-circular and Qhull picks the diagonals
-arbitrarily; they stay host geometry and out of scope (and with
-`fill_missing`, `inner_box` of a map that holds NaN).
+`resample_map`, `compose_maps` and the `interpolate_first=True` branch of
+`fill_missing` triangulate the regular lattice, where every quad is
+co-circular and Qhull picks the diagonals arbitrarily; they stay host geometry
+and out of scope (and with that branch, `inner_box` of a map that holds NaN).
+`fill_missing(extrapolate=True, interpolate_first=False)` never touches Qhull:
+every invalid node takes the nearest valid node, an exact integer feature
+transform on the device with a stated tie rule.
 """
 from __future__ import annotations
 
@@ -422,9 +426,10 @@ def inner_box(coord_map, box, stride):
   """Returns a box within which all nodes are mapped to by the map
   (map_utils.py:345-389), for maps WITHOUT NaN.
 
-  The reference first extrapolates invalid entries with `fill_missing`, which
-  returns a NaN-free map unchanged; `fill_missing` has no parity contract (see
-  the module docstring), so a map that holds a NaN raises NotImplementedError.
+  The reference first extrapolates invalid entries with `fill_missing` and its
+  default `interpolate_first=True`, which returns a NaN-free map unchanged; that
+  branch has no parity contract (see the module docstring), so a map that holds
+  a NaN raises NotImplementedError.
   The device returns the max of the per-line minima and the min of the per-line
   maxima of the absolute map along x, y[, z] in the map's dtype; the
   reference's `//` expressions are applied to NumPy scalars of that dtype.
@@ -449,6 +454,89 @@ def inner_box(coord_map, box, stride):
   z0 = int(-(-z0 // stride[0]))
   z1 = z1 // stride[0]
   return _make_box(box, (x0, y0, z0), (x1 - x0 + 1, y1 - y0 + 1, z1 - z0 + 1))
+
+
+def fill_missing(coord_map, *, extrapolate=False, invalid_to_zero=False,
+                 interpolate_first=True) -> DeviceArray:
+  """Fills missing entries of a [2 or 3, z, y, x] coordinate map
+  (map_utils.py:227-304), without the reference's Delaunay interpolation.
+
+  Name, keywords and defaults are the reference's; `coord_map` is NumPy, a CUDA
+  tensor or a DeviceArray, float32 or float64 (TypeError otherwise; other
+  channel counts raise ValueError), is never written, and the result is a new
+  DeviceArray of its dtype.  A 2-channel map is filled per z slice, a 3-channel
+  map as one volume.
+
+  * A map without NaN is returned unchanged (a copy); `inf` entries stay.
+  * `interpolate_first=True` -- the default -- on a map that holds NaN raises
+    NotImplementedError: that branch triangulates the regular lattice, whose
+    quads are co-circular, so Qhull's pick of diagonals is arbitrary and the
+    result has no parity contract.  So `fill_missing(m)` with the default
+    arguments raises for a map with NaN; pass `interpolate_first=False`.
+  * A node is valid when all its channels are finite (`inf` makes it invalid).
+    A slice (volume) without a valid node becomes all zeros with
+    `invalid_to_zero`, else all NaN with `extrapolate` (SciPy's
+    NearestNDInterpolator over an empty point set), else stays as it is.
+  * `interpolate_first=False, extrapolate=True`: every invalid node gets, in all
+    channels, the bits of the valid node at the smallest squared Euclidean
+    distance in node indices (isotropic, strides ignored; z counts for 3-channel
+    maps only).  Among equidistant nodes the lowest C-order index of [z,] y, x
+    wins -- SciPy's pick there is an artefact of its k-d tree, so the result
+    equals the reference's wherever the nearest node is unique.  Valid nodes
+    keep their bits.
+  * `interpolate_first=False, extrapolate=False`: only the `invalid_to_zero`
+    rule applies.
+
+  Distances are exact 32-bit integers: an axis holds at most 16384 nodes and
+  the map fewer than 2^31 nodes per channel (ValueError above).  Nothing comes
+  to the host except, with `interpolate_first=True`, the NaN flag.
+  """
+  if isinstance(coord_map, DeviceArray):
+    coord_map = coord_map.tensor
+  shape = tuple(coord_map.shape) if isinstance(coord_map, torch.Tensor) else np.shape(coord_map)
+  if len(shape) != 4 or shape[0] not in (2, 3):
+    raise ValueError(f'coord_map must be [2 or 3, z, y, x], got shape {tuple(shape)}')
+  dev = _dev.device()
+  if isinstance(coord_map, torch.Tensor):
+    if coord_map.dtype not in (torch.float32, torch.float64):
+      raise TypeError(f'fill_missing: float32 or float64 maps, got {coord_map.dtype}')
+    m = coord_map.to(dev).contiguous()
+  else:
+    arr = np.asarray(coord_map)
+    if arr.dtype not in (np.float32, np.float64):
+      raise TypeError(f'fill_missing: float32 or float64 maps, got {arr.dtype}')
+    m = _dev.upload(np.ascontiguousarray(arr), dev)
+  if min(shape[1:]) < 1:
+    raise ValueError(f'empty coord_map: {tuple(shape)}')
+  if max(shape[1:]) > _abi.FILL_MISSING_MAX_AXIS or m[0].numel() >= 2**31:
+    raise ValueError(
+        f'fill_missing: at most {_abi.FILL_MISSING_MAX_AXIS} nodes per axis and fewer than '
+        f'2^31 per channel, got shape {tuple(shape)}')
+  out = torch.empty_like(m)
+  has_nan = torch.empty(1, dtype=torch.int32, device=dev)
+  d = _abi.SfmFillMissingDesc()
+  d.ncomp = shape[0]
+  d.f64 = int(m.dtype == torch.float64)
+  d.shape = (C.c_int32 * 3)(*shape[1:])
+  # with interpolate_first the call only copies the map and reports the flag
+  d.invalid_to_zero = int(bool(invalid_to_zero) and not interpolate_first)
+  d.extrapolate = int(bool(extrapolate) and not interpolate_first)
+  d.coord_map = m.data_ptr()
+  d.out = out.data_ptr()
+  d.has_nan = has_nan.data_ptr()
+  lib = _abi.load()
+  ws = _dev.workspace(lib.sfm_fill_missing_nearest_workspace_bytes(C.byref(d)), dev)
+  d.workspace = ws.data_ptr()
+  d.workspace_bytes = ws.numel()
+  d.stream = _dev.stream_ptr()
+  _abi.check(lib.sfm_fill_missing_nearest(C.byref(d)))
+  if interpolate_first and int(has_nan.item()):
+    raise NotImplementedError(
+        'fill_missing: the map holds NaN and interpolate_first=True asks for a Delaunay '
+        'interpolation over the regular lattice, where every quad is co-circular and Qhull '
+        'picks the diagonals arbitrarily; it is not on the device.  '
+        'interpolate_first=False fills by the nearest valid node')
+  return DeviceArray(out)
 
 
 def make_affine_map(matrix, box, stride) -> DeviceArray:

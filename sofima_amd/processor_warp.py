@@ -16,12 +16,15 @@ reference's bit for bit (tests/golden/render3d.npz).
   blend_weights  <->  _get_dts             (:147-161)
   plan_render    <->  _load_tile_images    (:183-241), the box arithmetic
   render         <->  process              (:292-343)
+  fill_inverted  <->  the fill_missing call of _load_tile_images (:199-203)
 
 Array level, no volume stores.  Boxes are objects with `.start` / `.size` in
 xyz or (start, size) pairs; the boxes returned are `Box` tuples, which are both.
-The per-tile inverse maps (the reference's 3-D `invert_map` followed by the
-nearest-only `fill_missing`, :195-204) are inputs: they are mesh sized,
-computed once per tile, and depend on 3-D Qhull.
+The per-tile inverse maps (the reference's 3-D `invert_map`, :195-198) are
+inputs: they are mesh sized, computed once per tile, and depend on 3-D Qhull.
+`plan_render`, `render` and `TileRenderer` take them without NaN, i.e. after the
+nearest-only `fill_missing` of :199-203, which `fill_inverted` runs on the
+device.
 
 Kept from the reference: a voxel no tile reaches is 0; a NaN or out-of-range
 dense coordinate samples 0 for image and weight; with `margin > 0` a tile on the
@@ -190,6 +193,25 @@ def plan_render(box, boxes, inverted, tile_idx_to_xy, tile_shape_zyx: Sequence[i
       continue
     plan.append((i, data_box, tg_box, local_warp_box, sub_box))
   return plan
+
+
+def fill_inverted(inverted) -> dict[int, tuple[Box, DeviceArray]]:
+  """{i: (tg_box, inverted_map)} with the maps' NaN nodes filled by the nearest
+  valid node, the reference's `fill_missing(extrapolate=True,
+  interpolate_first=False)` of processor/warp.py:199-203, on the device.
+
+  inverted: {i: (tg_box, [3, z, y, x] map)} as the 3-D `invert_map` leaves them
+  (NaN outside the hull of the tile's nodes; NumPy, torch or DeviceArray).
+  Returns float64 DeviceArrays, ready for `plan_render` / `TileRenderer`.
+  """
+  filled = {}
+  for i, (tg_box, inv) in inverted.items():
+    inv = _array(inv)
+    inv = inv.to(torch.float64) if isinstance(inv, torch.Tensor) else np.asarray(
+        inv, dtype=np.float64)
+    filled[i] = _as_box(tg_box), map_utils.fill_missing(
+        inv, extrapolate=True, interpolate_first=False)
+  return filled
 
 
 _DTYPES = {np.dtype(np.uint8): _abi.DTYPE_U8, np.dtype(np.uint16): _abi.DTYPE_U16,
