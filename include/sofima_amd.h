@@ -52,7 +52,9 @@ extern "C" {
                                    which the mode entry points read padded
                                    coefficients for two modes; off: unchanged),
                                    and sfm_fill_missing_nearest with
-                                   sfm_fill_missing_nearest_workspace_bytes */
+                                   sfm_fill_missing_nearest_workspace_bytes, and
+                                   sfm_resample_map with
+                                   sfm_resample_map_workspace_bytes */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -539,6 +541,46 @@ size_t sfm_invert_map_workspace_bytes(const SfmInvertMapDesc* desc);
  * be NULL when the output lattice is empty (status is still written).
  * Asynchronous: read status after the stream has finished. */
 int sfm_invert_map(const SfmInvertMapDesc* desc, double* out);
+
+/* ------------------------------------------------------------------------
+ * Resampling of an in-plane coordinate map (or a flow) onto another lattice,
+ * the upsampling between two flow resolutions.  Replaces the linear branch of
+ * map_utils.resample_map (map_utils.py:490-546) on the engine of
+ * sfm_invert_map: per z slice, the nodes whose channel 0 is finite, at
+ * ((j + src_start_x) * src_stride, (i + src_start_y) * src_stride), are
+ * triangulated (Delaunay, exact predicates, ties broken in node-index order:
+ * a full lattice quad is split from (i, j + 1) to (i + 1, j)) and both
+ * channels are interpolated linearly, l0 * v0 + l1 * v1 + l2 * v2 in double,
+ * at the queries ((u + dst_start_x) * dst_stride, (w + dst_start_y) *
+ * dst_stride).  The result is the interpolant of ONE Delaunay triangulation
+ * of the valid nodes: equal to any other's wherever all Delaunay
+ * triangulations agree, one of their values elsewhere.  Queries outside the
+ * convex hull, slices with fewer than 3 valid or only collinear nodes: NaN.  A
+ * NaN in channel 1 of a valid node propagates.  status[z] and the limits are
+ * those of sfm_invert_map (SFM_INVMAP_*); a lattice cannot fold.
+ * ---------------------------------------------------------------------- */
+typedef struct SfmResampleMapDesc {
+  int32_t shape[3];             /* z, y, x of coord_map                      */
+  int32_t dst_shape[2];         /* y, x of the output lattice                */
+  int32_t src_start[2];         /* y, x of src_box.start                     */
+  int32_t dst_start[2];         /* y, x of dst_box.start                     */
+  double src_stride;            /* finite and > 0                            */
+  double dst_stride;            /* finite and > 0                            */
+  int32_t f64;                  /* coord_map and out are double, else float  */
+  const void* coord_map;        /* device [2, z, y, x]                       */
+  int32_t* status;              /* device [z], caller-owned, written         */
+  void* workspace;              /* sfm_resample_map_workspace_bytes()        */
+  size_t workspace_bytes;
+  void* stream;
+} SfmResampleMapDesc;
+
+/* Host arithmetic only (callable without a GPU); 0 for a NULL descriptor or
+ * an empty shape. */
+size_t sfm_resample_map_workspace_bytes(const SfmResampleMapDesc* desc);
+/* out: device [2, z, dst y, dst x] of coord_map's type; must not overlap
+ * coord_map; may be NULL when the output lattice is empty (status is still
+ * written).  Asynchronous: read status after the stream has finished. */
+int sfm_resample_map(const SfmResampleMapDesc* desc, void* out);
 
 /* ------------------------------------------------------------------------
  * Fold / stretch detection on a relaxed mesh, the step after relaxation.

@@ -173,6 +173,23 @@ class SfmInvertMapDesc(C.Structure):
   ]
 
 
+class SfmResampleMapDesc(C.Structure):
+  _fields_ = [
+      ('shape', i32 * 3),
+      ('dst_shape', i32 * 2),
+      ('src_start', i32 * 2),
+      ('dst_start', i32 * 2),
+      ('src_stride', C.c_double),
+      ('dst_stride', C.c_double),
+      ('f64', i32),
+      ('coord_map', C.c_void_p),
+      ('status', C.c_void_p),
+      ('workspace', C.c_void_p),
+      ('workspace_bytes', C.c_size_t),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmMaskIrregularDesc(C.Structure):
   _fields_ = [
       ('shape', i32 * 2),
@@ -678,6 +695,8 @@ SIGNATURES = {
     'sfm_filter_tile_flows_max_nodes': (C.c_int, []),
     'sfm_invert_map_workspace_bytes': (C.c_size_t, [C.POINTER(SfmInvertMapDesc)]),
     'sfm_invert_map': (C.c_int, [C.POINTER(SfmInvertMapDesc), C.c_void_p]),
+    'sfm_resample_map_workspace_bytes': (C.c_size_t, [C.POINTER(SfmResampleMapDesc)]),
+    'sfm_resample_map': (C.c_int, [C.POINTER(SfmResampleMapDesc), C.c_void_p]),
     'sfm_mask_irregular': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,
                                      C.c_void_p]),
     'sfm_mask_irregular_f64': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,

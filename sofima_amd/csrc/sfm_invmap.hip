@@ -1,6 +1,7 @@
 // Inversion of in-plane coordinate maps on the device:
 //
-//   sfm_invert_map  <->  map_utils.invert_map, 2-D branch (map_utils.py:392-463)
+//   sfm_invert_map    <->  map_utils.invert_map, 2-D branch (map_utils.py:392-463)
+//   sfm_resample_map  <->  map_utils.resample_map, linear (map_utils.py:490-546)
 //
 // The reference triangulates the absolute positions of the valid nodes of a z
 // slice with Qhull and interpolates the source lattice coordinates linearly
@@ -35,6 +36,23 @@
 // are broken by a symbolic perturbation of the lifting in node-index order, so
 // every decision is consistent and the result is a Delaunay triangulation of
 // the (rounded) points.
+//
+// Modes.  The engine triangulates points that carry values and interpolates
+// them at a query lattice; what the points, the queries and the values are is
+// a compile-time mode (Mode) of steps 1, 5 and 6 and of nothing else:
+//
+//   kInvert    points: the deformed positions of the nodes; queries: the dst
+//              lattice trunc(u * stride); values: the source lattice
+//              coordinates, made relative
+//   kResample  points: the src lattice ((j + start) * src_stride) at the nodes
+//              whose channel 0 is finite; queries: the dst lattice
+//              ((u + start) * dst_stride); values: the two channels of the map
+//              itself, stored in the map's type
+//
+// In kResample every full quad is an exact square: the in-circle test ties and
+// the perturbation (lowest node id first: corner a of the quad) gives
+// orient(b, c, d) > 0, so the diagonal is always b-d, from (i, j + 1) to
+// (i + 1, j).  No quad can fold there.
 #include "sfm_common.h"
 
 #include <hip/hip_runtime.h>
@@ -77,11 +95,15 @@ struct SliceInfo {
   int qcount;      // triangles that contain the probe point
 };
 
+enum Mode : int { kInvert = 0, kResample = 1 };
+
 struct Args {
-  const double* map;  // [2, Z, H, W]
+  const void* map;    // [2, Z, H, W]: double (kInvert), float or double (kResample)
   int Z, H, W, Hd, Wd;
-  int sy0, sx0;       // src start - dst start (y, x)
-  double sy, sx;
+  int sy0, sx0;       // kInvert: src start - dst start (y, x); kResample: src start
+  double sy, sx;      // stride of the node lattice
+  int qy0, qx0;       // kResample: dst start (y, x)
+  double qs;          // kResample: stride of the query lattice
   int* status;
   double2* pos;       // [Z, H, W] absolute, NaN when invalid
   longlong2* qpos;    // [Z, H, W] on the predicate grid
@@ -96,7 +118,7 @@ struct Args {
   unsigned long long* tkeys;  // [Z, capTH] triangle hash, 0 empty
   unsigned* queue;    // [Z, capQ] edge keys
   unsigned long long* qkeys;  // [Z, Hd, Wd] winning triangle
-  double* out;        // [2, Z, Hd, Wd]
+  void* out;          // [2, Z, Hd, Wd], of the map's type
   int capB, capT, capQ;
   unsigned capE, capTH;
 };
@@ -305,6 +327,20 @@ __device__ __forceinline__ bool wave_one_slice(int z) {
   return __all(z == z0 || z < 0) && z0 >= 0;
 }
 
+// Query (u, w) of the output lattice, one axis at a time.
+template <int MODE>
+__device__ __forceinline__ double query_x(const Args& a, int u) {
+  if constexpr (MODE == kInvert) return trunc((double)u * a.sx);
+  return (double)((long long)u + a.qx0) * a.qs;
+}
+
+template <int MODE>
+__device__ __forceinline__ double query_y(const Args& a, int w) {
+  if constexpr (MODE == kInvert) return trunc((double)w * a.sy);
+  return (double)((long long)w + a.qy0) * a.qs;
+}
+
+template <int MODE, typename T>
 __global__ void __launch_bounds__(kBlock) im_prep_kernel(Args a) {
   const long long hw = (long long)a.H * a.W;
   const long long n = (long long)a.Z * hw;
@@ -315,13 +351,22 @@ __global__ void __launch_bounds__(kBlock) im_prep_kernel(Args a) {
   if (live) {
     const int r = (int)(t % hw);
     const int i = r / a.W, j = r % a.W;
-    const double rx = a.map[t], ry = a.map[n + t];
-    const bool valid = isfinite(rx) && isfinite(ry);
+    const T* map = static_cast<const T*>(a.map);
+    bool valid;
     double2 p;
-    if (valid) {
-      // to_absolute: rel + (j * sx + start_x * sx), same for y
-      p.x = rx + ((double)j * a.sx + (double)a.sx0 * a.sx);
-      p.y = ry + ((double)i * a.sy + (double)a.sy0 * a.sy);
+    if constexpr (MODE == kInvert) {
+      const double rx = map[t], ry = map[n + t];
+      valid = isfinite(rx) && isfinite(ry);
+      if (valid) {
+        // to_absolute: rel + (j * sx + start_x * sx), same for y
+        p.x = rx + ((double)j * a.sx + (double)a.sx0 * a.sx);
+        p.y = ry + ((double)i * a.sy + (double)a.sy0 * a.sy);
+      }
+    } else {
+      // the reference looks at channel 0 only; the integer sum, then one product
+      valid = isfinite(map[t]);
+      p.x = (double)((long long)j + a.sx0) * a.sx;
+      p.y = (double)((long long)i + a.sy0) * a.sy;
     }
     if (valid && isfinite(p.x) && isfinite(p.y)) {
       int ex, ey;
@@ -757,11 +802,17 @@ __global__ void __launch_bounds__(kBlock) im_verify_nodes_kernel(Args a) {
   if (!in_r) atomicOr(&a.status[z], kStUnused);
 }
 
-// Query lattice range [lo, hi] that can hold a triangle spanning [mn, mx].
-__device__ __forceinline__ void query_range(double mn, double mx, double s, int n, int* lo,
-                                            int* hi) {
-  const double margin = 1.0 + ceil(1.0 / s);
+// Query lattice range [lo, hi] that can hold a triangle spanning [mn, mx]:
+// queries at trunc(u * s) (kInvert) or (u + q0) * s (kResample).
+template <int MODE>
+__device__ __forceinline__ void query_range(double mn, double mx, double s, int q0, int n,
+                                            int* lo, int* hi) {
+  const double margin = MODE == kInvert ? 1.0 + ceil(1.0 / s) : 2.0;
   double l = floor(mn / s) - margin, h = ceil(mx / s) + margin;
+  if constexpr (MODE == kResample) {
+    l -= (double)q0;
+    h -= (double)q0;
+  }
   // clamp both ends before the conversion (an empty range stays empty)
   l = l < 0 ? 0 : (l > n ? n : l);
   h = h > n - 1 ? n - 1 : (h < -1 ? -1 : h);
@@ -771,6 +822,7 @@ __device__ __forceinline__ void query_range(double mn, double mx, double s, int 
 
 // Scatters triangle v (keyed `key`) over the query lattice of slice z; lanes
 // [lane0, lane0 + nlanes) share the work.
+template <int MODE>
 __device__ void scatter(const Args& a, int z, const int* v, unsigned long long key, int lane0,
                         int nlanes) {
   const long long base = (long long)z * a.H * a.W;
@@ -788,8 +840,13 @@ __device__ void scatter(const Args& a, int z, const int* v, unsigned long long k
     mxy = fmax(mxy, p.y);
   }
   int u0, u1, w0, w1;
-  query_range(mnx, mxx, a.sx, a.Wd, &u0, &u1);
-  query_range(mny, mxy, a.sy, a.Hd, &w0, &w1);
+  if constexpr (MODE == kInvert) {
+    query_range<MODE>(mnx, mxx, a.sx, 0, a.Wd, &u0, &u1);
+    query_range<MODE>(mny, mxy, a.sy, 0, a.Hd, &w0, &w1);
+  } else {
+    query_range<MODE>(mnx, mxx, a.qs, a.qx0, a.Wd, &u0, &u1);
+    query_range<MODE>(mny, mxy, a.qs, a.qy0, a.Hd, &w0, &w1);
+  }
   if (u0 > u1 || w0 > w1) return;
   const int nu = u1 - u0 + 1;
   const long long cnt = (long long)nu * (w1 - w0 + 1);
@@ -797,7 +854,7 @@ __device__ void scatter(const Args& a, int z, const int* v, unsigned long long k
   const double lim = 2305843009213693952.0;  // 2^61
   for (long long c = lane0; c < cnt; c += nlanes) {
     const int u = u0 + (int)(c % nu), w = w0 + (int)(c / nu);
-    const double qx = ldexp(trunc((double)u * a.sx), g), qy = ldexp(trunc((double)w * a.sy), g);
+    const double qx = ldexp(query_x<MODE>(a, u), g), qy = ldexp(query_y<MODE>(a, w), g);
     if (!(fabs(qx) < lim && fabs(qy) < lim)) continue;
     const ll X = llrint(qx), Y = llrint(qy);
     bool in = true;
@@ -807,6 +864,7 @@ __device__ void scatter(const Args& a, int z, const int* v, unsigned long long k
   }
 }
 
+template <int MODE>
 __global__ void __launch_bounds__(kBlock) im_scatter_r_kernel(Args a) {
   const int qw = a.W - 1, qh = a.H - 1;
   const long long per = (long long)qh * qw;
@@ -820,11 +878,12 @@ __global__ void __launch_bounds__(kBlock) im_scatter_r_kernel(Args a) {
     int k[3], v[3];
     quad_tri(s, h, k);
     for (int m = 0; m < 3; ++m) v[m] = corner(a.W, i, j, k[m]);
-    scatter(a, z, v, (unsigned long long)q << 1 | h, 0, 1);
+    scatter<MODE>(a, z, v, (unsigned long long)q << 1 | h, 0, 1);
   }
 }
 
 // One wave per triangle outside R (its bounding box can span the lattice).
+template <int MODE>
 __global__ void __launch_bounds__(kBlock) im_scatter_o_kernel(Args a) {
   const int z = blockIdx.y;
   const int n = a.info[z].ntri;
@@ -836,10 +895,11 @@ __global__ void __launch_bounds__(kBlock) im_scatter_o_kernel(Args a) {
     const unsigned long long key = 1ull << 63 | (unsigned long long)tr.x << (2 * kNodeBits) |
                                    (unsigned long long)tr.y << kNodeBits |
                                    (unsigned long long)tr.z;
-    scatter(a, z, v, key, lane, 64);
+    scatter<MODE>(a, z, v, key, lane, 64);
   }
 }
 
+template <int MODE, typename T>
 __global__ void __launch_bounds__(kBlock) im_gather_kernel(Args a) {
   const long long per = (long long)a.Hd * a.Wd;
   const long long n = (long long)a.Z * per;
@@ -868,12 +928,19 @@ __global__ void __launch_bounds__(kBlock) im_gather_kernel(Args a) {
     double vx[3], vy[3];
     for (int m = 0; m < 3; ++m) {
       p[m] = a.pos[base + v[m]];
-      const int i = v[m] / a.W, j = v[m] % a.W;
-      // the reference's source coordinates live in an integer array
-      vx[m] = trunc((double)(j + a.sx0) * a.sx);
-      vy[m] = trunc((double)(i + a.sy0) * a.sy);
+      if constexpr (MODE == kInvert) {
+        const int i = v[m] / a.W, j = v[m] % a.W;
+        // the reference's source coordinates live in an integer array
+        vx[m] = trunc((double)(j + a.sx0) * a.sx);
+        vy[m] = trunc((double)(i + a.sy0) * a.sy);
+      } else {
+        // the map's own channels; a NaN in channel 1 propagates
+        const T* map = static_cast<const T*>(a.map);
+        vx[m] = (double)map[base + v[m]];
+        vy[m] = (double)map[(long long)a.Z * a.H * a.W + base + v[m]];
+      }
     }
-    const double qx = trunc((double)u * a.sx), qy = trunc((double)w * a.sy);
+    const double qx = query_x<MODE>(a, u), qy = query_y<MODE>(a, w);
     const double e1x = p[1].x - p[0].x, e1y = p[1].y - p[0].y;
     const double e2x = p[2].x - p[0].x, e2y = p[2].y - p[0].y;
     const double dx = qx - p[0].x, dy = qy - p[0].y;
@@ -881,12 +948,17 @@ __global__ void __launch_bounds__(kBlock) im_gather_kernel(Args a) {
     const double l1 = (dx * e2y - dy * e2x) / det;
     const double l2 = (e1x * dy - e1y * dx) / det;
     const double l0 = 1.0 - l1 - l2;
-    // to_relative
-    ox = (l0 * vx[0] + l1 * vx[1] + l2 * vx[2]) - (double)u * a.sx;
-    oy = (l0 * vy[0] + l1 * vy[1] + l2 * vy[2]) - (double)w * a.sy;
+    ox = l0 * vx[0] + l1 * vx[1] + l2 * vx[2];
+    oy = l0 * vy[0] + l1 * vy[1] + l2 * vy[2];
+    if constexpr (MODE == kInvert) {
+      // to_relative
+      ox = ox - (double)u * a.sx;
+      oy = oy - (double)w * a.sy;
+    }
   }
-  a.out[(long long)z * per + r] = ox;
-  a.out[n + (long long)z * per + r] = oy;
+  T* out = static_cast<T*>(a.out);
+  out[(long long)z * per + r] = (T)ox;
+  out[n + (long long)z * per + r] = (T)oy;
 }
 
 unsigned pow2_at_least(unsigned long long v) {
@@ -902,12 +974,12 @@ struct InvLayout {
   unsigned capE, capTH;
 };
 
-InvLayout invmap_layout(const SfmInvertMapDesc* d) {
+InvLayout invmap_layout(const int32_t* shape, const int32_t* dst_shape) {
   InvLayout w{};
-  const size_t Z = d->shape[0], H = d->shape[1], W = d->shape[2];
+  const size_t Z = shape[0], H = shape[1], W = shape[2];
   const size_t nodes = Z * H * W, hw = H * W;
   const size_t quads = Z * (H > 1 ? H - 1 : 0) * (W > 1 ? W - 1 : 0);
-  const size_t queries = Z * (size_t)d->dst_shape[0] * d->dst_shape[1];
+  const size_t queries = Z * (size_t)dst_shape[0] * dst_shape[1];
   w.capB = (int)(hw < (size_t)kMaxB ? hw : (size_t)kMaxB);
   w.capT = 2 * w.capB + 8;
   w.capQ = 3 * w.capT + 2 * w.capB + 8;
@@ -939,52 +1011,36 @@ InvLayout invmap_layout(const SfmInvertMapDesc* d) {
 
 unsigned blocks(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-}  // namespace
-
-extern "C" size_t sfm_invert_map_workspace_bytes(const SfmInvertMapDesc* d) {
-  if (!d) return 0;
+// The shape and stride checks of both entry points; 0 when they pass.
+int check_shapes(const char* name, const int32_t* shape, const int32_t* dst_shape, double s0,
+                 double s1) {
   for (int i = 0; i < 3; ++i)
-    if (d->shape[i] < 1) return 0;
-  if (d->dst_shape[0] < 0 || d->dst_shape[1] < 0) return 0;
-  return invmap_layout(d).bytes;
+    if (shape[i] < 1) return sfm::fail(SFM_ERR_INVALID, "%s: bad shape", name);
+  if (dst_shape[0] < 0 || dst_shape[1] < 0)
+    return sfm::fail(SFM_ERR_INVALID, "%s: bad output shape", name);
+  if (!(s0 > 0.0) || !(s1 > 0.0) || !std::isfinite(s0) || !std::isfinite(s1))
+    return sfm::fail(SFM_ERR_INVALID, "%s: strides must be finite and positive", name);
+  const long long hw = (long long)shape[1] * shape[2];
+  if (hw > (1LL << kNodeBits))
+    return sfm::fail(SFM_ERR_INVALID, "%s: %lld nodes per slice exceed 2^21", name, hw);
+  if (hw * shape[0] > 0x7fffffffLL ||
+      (long long)dst_shape[0] * dst_shape[1] * shape[0] > 0x7fffffffLL)
+    return sfm::fail(SFM_ERR_INVALID, "%s: more than 2^31 - 1 nodes", name);
+  return SFM_OK;
 }
 
-extern "C" int sfm_invert_map(const SfmInvertMapDesc* d, double* out) {
-  // an empty dst box has no output to point at
-  if (!d || !d->coord_map || !d->status ||
-      (!out && d->dst_shape[0] > 0 && d->dst_shape[1] > 0))
-    return sfm::fail(SFM_ERR_INVALID, "invert_map: NULL argument");
-  for (int i = 0; i < 3; ++i)
-    if (d->shape[i] < 1) return sfm::fail(SFM_ERR_INVALID, "invert_map: bad shape");
-  if (d->dst_shape[0] < 0 || d->dst_shape[1] < 0)
-    return sfm::fail(SFM_ERR_INVALID, "invert_map: bad output shape");
-  if (!(d->stride[0] > 0.0) || !(d->stride[1] > 0.0) || !std::isfinite(d->stride[0]) ||
-      !std::isfinite(d->stride[1]))
-    return sfm::fail(SFM_ERR_INVALID, "invert_map: strides must be finite and positive");
-  const long long hw = (long long)d->shape[1] * d->shape[2];
-  if (hw > (1LL << kNodeBits))
-    return sfm::fail(SFM_ERR_INVALID, "invert_map: %lld nodes per slice exceed 2^21", hw);
-  if (hw * d->shape[0] > 0x7fffffffLL ||
-      (long long)d->dst_shape[0] * d->dst_shape[1] * d->shape[0] > 0x7fffffffLL)
-    return sfm::fail(SFM_ERR_INVALID, "invert_map: more than 2^31 - 1 nodes");
-  const InvLayout w = invmap_layout(d);
-  if (!d->workspace || d->workspace_bytes < w.bytes)
-    return sfm::fail(SFM_ERR_WORKSPACE, "invert_map workspace needs %zu bytes, got %zu",
-                     w.bytes, d->workspace_bytes);
-  char* ws = static_cast<char*>(d->workspace);
-  hipStream_t st = static_cast<hipStream_t>(d->stream);
-  Args a{};
-  a.map = d->coord_map;
-  a.Z = d->shape[0];
-  a.H = d->shape[1];
-  a.W = d->shape[2];
-  a.Hd = d->dst_shape[0];
-  a.Wd = d->dst_shape[1];
-  a.sy0 = d->src_start[0];
-  a.sx0 = d->src_start[1];
-  a.sy = d->stride[0];
-  a.sx = d->stride[1];
-  a.status = d->status;
+// Binds the workspace and runs the engine in one mode on a map of type T.
+// `a` carries the map, the lattices, the status and the output.
+template <int MODE, typename T>
+int run(Args a, const int32_t* shape, const int32_t* dst_shape, const InvLayout& w,
+        void* workspace, hipStream_t st) {
+  char* ws = static_cast<char*>(workspace);
+  a.Z = shape[0];
+  a.H = shape[1];
+  a.W = shape[2];
+  a.Hd = dst_shape[0];
+  a.Wd = dst_shape[1];
+  const long long hw = (long long)a.H * a.W;
   a.pos = reinterpret_cast<double2*>(ws + w.pos);
   a.qpos = reinterpret_cast<longlong2*>(ws + w.qpos);
   a.split = reinterpret_cast<unsigned char*>(ws + w.split);
@@ -998,7 +1054,6 @@ extern "C" int sfm_invert_map(const SfmInvertMapDesc* d, double* out) {
   a.tkeys = reinterpret_cast<unsigned long long*>(ws + w.tkeys);
   a.queue = reinterpret_cast<unsigned*>(ws + w.queue);
   a.qkeys = reinterpret_cast<unsigned long long*>(ws + w.qkeys);
-  a.out = out;
   a.capB = w.capB;
   a.capT = w.capT;
   a.capQ = w.capQ;
@@ -1016,7 +1071,7 @@ extern "C" int sfm_invert_map(const SfmInvertMapDesc* d, double* out) {
   if (queries > 0)
     SFM_HIP_CHECK(hipMemsetAsync(a.qkeys, 0xff, queries * sizeof(unsigned long long), st));
   hipLaunchKernelGGL(im_init_kernel, dim3(blocks(Z)), dim3(kBlock), 0, st, a);
-  hipLaunchKernelGGL(im_prep_kernel, dim3(blocks(nodes)), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((im_prep_kernel<MODE, T>), dim3(blocks(nodes)), dim3(kBlock), 0, st, a);
   hipLaunchKernelGGL(im_quant_kernel, dim3(blocks(nodes)), dim3(kBlock), 0, st, a);
   if (quads > 0)
     hipLaunchKernelGGL(im_quad_kernel, dim3(blocks(quads)), dim3(kBlock), 0, st, a);
@@ -1029,10 +1084,82 @@ extern "C" int sfm_invert_map(const SfmInvertMapDesc* d, double* out) {
   SFM_LAUNCH_CHECK();
   if (queries > 0) {
     if (quads > 0)
-      hipLaunchKernelGGL(im_scatter_r_kernel, dim3(blocks(quads)), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(im_scatter_o_kernel, dim3(64, (unsigned)Z), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(im_gather_kernel, dim3(blocks(queries)), dim3(kBlock), 0, st, a);
+      hipLaunchKernelGGL(im_scatter_r_kernel<MODE>, dim3(blocks(quads)), dim3(kBlock), 0, st,
+                         a);
+    hipLaunchKernelGGL(im_scatter_o_kernel<MODE>, dim3(64, (unsigned)Z), dim3(kBlock), 0, st,
+                       a);
+    hipLaunchKernelGGL((im_gather_kernel<MODE, T>), dim3(blocks(queries)), dim3(kBlock), 0, st,
+                       a);
     SFM_LAUNCH_CHECK();
   }
   return SFM_OK;
+}
+
+}  // namespace
+
+extern "C" size_t sfm_invert_map_workspace_bytes(const SfmInvertMapDesc* d) {
+  if (!d) return 0;
+  for (int i = 0; i < 3; ++i)
+    if (d->shape[i] < 1) return 0;
+  if (d->dst_shape[0] < 0 || d->dst_shape[1] < 0) return 0;
+  return invmap_layout(d->shape, d->dst_shape).bytes;
+}
+
+extern "C" int sfm_invert_map(const SfmInvertMapDesc* d, double* out) {
+  // an empty dst box has no output to point at
+  if (!d || !d->coord_map || !d->status ||
+      (!out && d->dst_shape[0] > 0 && d->dst_shape[1] > 0))
+    return sfm::fail(SFM_ERR_INVALID, "invert_map: NULL argument");
+  if (const int err = check_shapes("invert_map", d->shape, d->dst_shape, d->stride[0],
+                                   d->stride[1]))
+    return err;
+  const InvLayout w = invmap_layout(d->shape, d->dst_shape);
+  if (!d->workspace || d->workspace_bytes < w.bytes)
+    return sfm::fail(SFM_ERR_WORKSPACE, "invert_map workspace needs %zu bytes, got %zu",
+                     w.bytes, d->workspace_bytes);
+  Args a{};
+  a.map = d->coord_map;
+  a.sy0 = d->src_start[0];
+  a.sx0 = d->src_start[1];
+  a.sy = d->stride[0];
+  a.sx = d->stride[1];
+  a.status = d->status;
+  a.out = out;
+  return run<kInvert, double>(a, d->shape, d->dst_shape, w, d->workspace,
+                              static_cast<hipStream_t>(d->stream));
+}
+
+extern "C" size_t sfm_resample_map_workspace_bytes(const SfmResampleMapDesc* d) {
+  if (!d) return 0;
+  for (int i = 0; i < 3; ++i)
+    if (d->shape[i] < 1) return 0;
+  if (d->dst_shape[0] < 0 || d->dst_shape[1] < 0) return 0;
+  return invmap_layout(d->shape, d->dst_shape).bytes;
+}
+
+extern "C" int sfm_resample_map(const SfmResampleMapDesc* d, void* out) {
+  if (!d || !d->coord_map || !d->status ||
+      (!out && d->dst_shape[0] > 0 && d->dst_shape[1] > 0))
+    return sfm::fail(SFM_ERR_INVALID, "resample_map: NULL argument");
+  if (const int err = check_shapes("resample_map", d->shape, d->dst_shape, d->src_stride,
+                                   d->dst_stride))
+    return err;
+  const InvLayout w = invmap_layout(d->shape, d->dst_shape);
+  if (!d->workspace || d->workspace_bytes < w.bytes)
+    return sfm::fail(SFM_ERR_WORKSPACE, "resample_map workspace needs %zu bytes, got %zu",
+                     w.bytes, d->workspace_bytes);
+  Args a{};
+  a.map = d->coord_map;
+  a.sy0 = d->src_start[0];
+  a.sx0 = d->src_start[1];
+  a.sy = a.sx = d->src_stride;
+  a.qy0 = d->dst_start[0];
+  a.qx0 = d->dst_start[1];
+  a.qs = d->dst_stride;
+  a.status = d->status;
+  a.out = out;
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  if (d->f64)
+    return run<kResample, double>(a, d->shape, d->dst_shape, w, d->workspace, st);
+  return run<kResample, float>(a, d->shape, d->dst_shape, w, d->workspace, st);
 }

@@ -5,16 +5,23 @@ Drop-ins for `map_utils.compose_maps_fast` of the reference
 branch of `map_utils.invert_map` (:392-463) and the helpers that the
 reference's renderers call around them: `to_absolute` / `to_relative`
 (:150-224), `outer_box` (:307-342), `inner_box` (:345-389, maps without NaN),
-`make_affine_map` (:789-811) and the nearest-node branch of `fill_missing`
-(:227-304 with `interpolate_first=False`).  The helpers are one pass over
+`make_affine_map` (:789-811), the nearest-node branch of `fill_missing`
+(:227-304 with `interpolate_first=False`) and the linear `resample_map`
+(:490-546).  The helpers are one pass over
 memory each and take and return `DeviceArray`s, so a map produced by
 `invert_map` or `compose_maps_fast` is shifted or measured without a host
 round trip.  `invert_map` triangulates the deformed positions, so its Delaunay
 triangulation is unique and the device result has a parity contract.
 `resample_map`, `compose_maps` and the `interpolate_first=True` branch of
 `fill_missing` triangulate the regular lattice, where every quad is
-co-circular and Qhull picks the diagonals arbitrarily; they stay host geometry
-and out of scope (and with that branch, `inner_box` of a map that holds NaN).
+co-circular and Qhull picks the diagonals arbitrarily.  `resample_map` runs on
+the engine of `invert_map` under the contract that does exist there: the
+interpolant of one verified, deterministic Delaunay triangulation, equal to
+the reference wherever all Delaunay triangulations agree and one of the
+admissible values elsewhere (see its docstring).  `compose_maps` (arbitrary
+query points: point location) and the `interpolate_first=True` branch of
+`fill_missing` stay host geometry and out of scope (and with that branch,
+`inner_box` of a map that holds NaN).
 `fill_missing(extrapolate=True, interpolate_first=False)` never touches Qhull:
 every invalid node takes the nearest valid node, an exact integer feature
 transform on the device with a stated tie rule.
@@ -208,8 +215,7 @@ def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
   SofimaAmdError naming the first such slice and its reason, the refused
   slices, and the reason of each that differs; it is never answered wrongly.
   """
-  shape = tuple(int(v) for v in np.shape(coord_map)) if not isinstance(
-      coord_map, (torch.Tensor, DeviceArray)) else tuple(coord_map.shape)
+  shape = _map_shape(coord_map)
   if len(shape) != 4:
     raise ValueError(f'coord_map must be [2, z, y, x], got shape {shape}')
   dim = shape[0]
@@ -222,35 +228,84 @@ def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
   sy, sx = (float(v) for v in _as_vec(stride, dim))
   if not (np.isfinite(sx) and np.isfinite(sy) and sx > 0 and sy > 0):
     raise ValueError(f'stride must be finite and positive, got {stride}')
+  src_start, dst_start, dst_size = _engine_boxes(shape, src_box, dst_box)
+  dev = _dev.device()
+  m = _engine_map(coord_map, dev, keep_f32=False)
+  d = _abi.SfmInvertMapDesc()
+  d.src_start = _i32_pair('src_box.start - dst_box.start', src_start[1] - dst_start[1],
+                          src_start[0] - dst_start[0])
+  d.stride = (C.c_double * 2)(sy, sx)
+  lib = _abi.load()
+  out, status = _engine_run(d, lib.sfm_invert_map_workspace_bytes, lib.sfm_invert_map, m,
+                            dst_size, dev)
+  _raise_refused('invert_map', status)
+  return DeviceArray(out)
+
+
+# -- what invert_map and resample_map share: one engine, one descriptor tail --
+
+
+def _map_shape(coord_map):
+  if isinstance(coord_map, (torch.Tensor, DeviceArray)):
+    return tuple(coord_map.shape)
+  return tuple(int(v) for v in np.shape(coord_map))
+
+
+def _engine_boxes(shape, src_box, dst_box):
+  """(src start xy.., dst start xy.., dst size xy..) of the boxes of a
+  [2, z, y, x] map, checked against its shape."""
   src_start, src_size = _box_xy(src_box, 'src_box')
   dst_start, dst_size = _box_xy(dst_box, 'dst_box')
   if (shape[3], shape[2]) != (src_size[0], src_size[1]):
     raise ValueError(f'box shape ({src_size}) mismatch with coord map ({shape})')
   if min(shape[1:]) < 1 or dst_size[0] < 0 or dst_size[1] < 0:
     raise ValueError(f'empty map or box: {shape}, {dst_size}')
-  dev = _dev.device()
+  return src_start, dst_start, dst_size
+
+
+def _engine_map(coord_map, dev, keep_f32):
+  """The map as a contiguous device tensor: float64, or with `keep_f32` its own
+  float32 / float64 (a resident contiguous tensor of that type is not copied)."""
   if isinstance(coord_map, DeviceArray):
     coord_map = coord_map.tensor
   if isinstance(coord_map, torch.Tensor):
-    m = coord_map.to(device=dev, dtype=torch.float64).contiguous()
-  else:
-    m = _dev.upload(np.ascontiguousarray(np.asarray(coord_map, dtype=np.float64)), dev)
-  d = _abi.SfmInvertMapDesc()
-  d.shape = (C.c_int32 * 3)(*shape[1:])
+    f64 = not keep_f32 or coord_map.dtype == torch.float64
+    return coord_map.to(device=dev, dtype=torch.float64 if f64 else torch.float32).contiguous()
+  host = np.asarray(coord_map)
+  f64 = not keep_f32 or host.dtype == np.float64
+  return _dev.upload(np.ascontiguousarray(host, dtype=np.float64 if f64 else np.float32), dev)
+
+
+def _i32_pair(name, y, x):
+  """A (y, x) pair of the descriptor; ctypes would truncate silently."""
+  for v in (y, x):
+    if not -2**31 <= v < 2**31:
+      raise ValueError(f'{name} {v} does not fit 32 bits')
+  return (C.c_int32 * 2)(y, x)
+
+
+def _engine_run(d, workspace_bytes, run, m, dst_size, dev):
+  """Fills the part of the descriptor the two entry points share (shapes, map,
+  status, workspace, stream) and launches; returns (out, status [z] int32) of
+  the map's dtype, both device tensors, without reading the status."""
+  nz = int(m.shape[1])
+  d.shape = (C.c_int32 * 3)(*m.shape[1:])
   d.dst_shape = (C.c_int32 * 2)(dst_size[1], dst_size[0])
-  d.src_start = (C.c_int32 * 2)(src_start[1] - dst_start[1], src_start[0] - dst_start[0])
-  d.stride = (C.c_double * 2)(sy, sx)
   d.coord_map = m.data_ptr()
-  status = torch.empty(shape[1], dtype=torch.int32, device=dev)
+  status = torch.empty(nz, dtype=torch.int32, device=dev)
   d.status = status.data_ptr()
-  lib = _abi.load()
-  nbytes = lib.sfm_invert_map_workspace_bytes(C.byref(d))
-  ws = _dev.workspace(nbytes, dev)
+  ws = _dev.workspace(workspace_bytes(C.byref(d)), dev)
   d.workspace = ws.data_ptr()
   d.workspace_bytes = ws.numel()
   d.stream = _dev.stream_ptr()
-  out = torch.empty((2, shape[1], dst_size[1], dst_size[0]), dtype=torch.float64, device=dev)
-  _abi.check(lib.sfm_invert_map(C.byref(d), out.data_ptr()))
+  out = torch.empty((2, nz, dst_size[1], dst_size[0]), dtype=m.dtype, device=dev)
+  _abi.check(run(C.byref(d), out.data_ptr()))
+  return out, status
+
+
+def _raise_refused(name, status):
+  """Reads the per-slice status of the triangulation engine (the one host sync
+  of `invert_map` / `resample_map`) and raises for refused slices."""
   st = status.cpu().numpy()
   bad = np.flatnonzero(st)
   if bad.size:
@@ -263,8 +318,70 @@ def invert_map(coord_map, src_box, dst_box, stride) -> DeviceArray:
       # the listed slices that were refused for another reason than the first
       other = ''.join(f'; slice {int(k)}: {why(k)}' for k in bad[1:8] if st[k] != st[z])
       more = f' ({bad.size} slices refused: {bad.tolist()[:8]}{other})'
-    raise _abi.SofimaAmdError(f'invert_map: slice {z} refused: {why(z)}{more}')
+    raise _abi.SofimaAmdError(f'{name}: slice {z} refused: {why(z)}{more}')
+
+
+def resample_map(coord_map, src_box, dst_box, src_stride: float, dst_stride: float,
+                 method='linear') -> DeviceArray:
+  """Resamples a [2, z, y, x] coordinate map (or flow) onto another lattice.
+
+  Same signature and box convention as the reference (map_utils.py:490-546):
+  `src_box` / `dst_box` have `.start` / `.size` in xyz order (only x and y are
+  used), node (i, j) of the map lies at ((j + src start x) * src_stride,
+  (i + src start y) * src_stride) and the result is sampled at
+  ((u + dst start x) * dst_stride, (w + dst start y) * dst_stride).  Per z
+  slice the nodes whose channel 0 is finite are triangulated (Delaunay) and
+  both channels are interpolated linearly in float64; queries outside the
+  convex hull and slices with fewer than 3 valid or only collinear nodes are
+  NaN, and a NaN in channel 1 of a valid node propagates.  `coord_map` is a
+  NumPy array, a CUDA tensor or a DeviceArray, float32 or float64; a resident
+  contiguous input is read where it lies and never modified.  Returns a
+  [2, z, dst y, dst x] DeviceArray of the input's dtype; an empty dst box gives
+  an empty result.
+
+  Contract.  The valid nodes lie on a lattice, where Delaunay triangulations
+  are not unique (every full quad is co-circular) and Qhull's choice is
+  arbitrary.  The device interpolates over one verified, deterministic
+  Delaunay triangulation (a full quad is split from (i, j + 1) to (i + 1, j)):
+  the result equals the reference wherever all Delaunay triangulations agree
+  (nodes, cell edges, affine data, ...) and is the interpolant over some
+  Delaunay triangle that contains the query everywhere else.
+
+  Only `method='linear'` is built: 'nearest' is a k-d tree with arbitrary ties
+  on a lattice and 'cubic' is Clough-Tocher; both raise NotImplementedError.
+  A slice with more than 7936 boundary nodes raises SofimaAmdError naming the
+  slice and the reason, as in `invert_map`; it is never answered wrongly.
+  """
+  if method != 'linear':
+    raise NotImplementedError(
+        f"resample_map: method {method!r} is not on the device (only 'linear')")
+  out, status = _resample_launch(coord_map, src_box, dst_box, src_stride, dst_stride)
+  _raise_refused('resample_map', status)
   return DeviceArray(out)
+
+
+def _resample_launch(coord_map, src_box, dst_box, src_stride, dst_stride):
+  """`resample_map` up to the status read: (out, status [z] int32), both device
+  tensors; a slice with a non-zero status holds nothing to be used."""
+  shape = _map_shape(coord_map)
+  if len(shape) != 4 or shape[0] != 2:
+    raise ValueError(f'coord_map must be [2, z, y, x], got shape {shape}')
+  src_stride, dst_stride = float(src_stride), float(dst_stride)
+  for s in (src_stride, dst_stride):
+    if not (np.isfinite(s) and s > 0):
+      raise ValueError(f'strides must be finite and positive, got {src_stride}, {dst_stride}')
+  src_start, dst_start, dst_size = _engine_boxes(shape, src_box, dst_box)
+  dev = _dev.device()
+  m = _engine_map(coord_map, dev, keep_f32=True)
+  d = _abi.SfmResampleMapDesc()
+  d.src_start = _i32_pair('src_box.start', src_start[1], src_start[0])
+  d.dst_start = _i32_pair('dst_box.start', dst_start[1], dst_start[0])
+  d.src_stride = src_stride
+  d.dst_stride = dst_stride
+  d.f64 = int(m.dtype == torch.float64)
+  lib = _abi.load()
+  return _engine_run(d, lib.sfm_resample_map_workspace_bytes, lib.sfm_resample_map, m,
+                     dst_size, dev)
 
 
 # -- geometry helpers: to_absolute / to_relative / outer_box / inner_box /

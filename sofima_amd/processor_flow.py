@@ -1,12 +1,16 @@
-"""The section loops around the flow estimator: `EstimateFlow` and
-`EstimateMissingFlow`, at array level.
+"""The section loops around the flow estimator: `EstimateFlow`,
+`EstimateMissingFlow` and `ReconcileAndFilterFlows`, at array level.
 
 Drop-ins for the compute part of `processor/flow.py`:
 
-  estimate_flow          <-> EstimateFlow.process         (processor/flow.py:163-245)
-  missing_flow_geometry  <-> the box arithmetic of
-                             EstimateMissingFlow.process  (:634-737)
-  estimate_missing_flow  <-> its section / look-back loop (:666-828)
+  estimate_flow               <-> EstimateFlow.process         (processor/flow.py:163-245)
+  missing_flow_geometry       <-> the box arithmetic of
+                                  EstimateMissingFlow.process  (:634-737)
+  estimate_missing_flow       <-> its section / look-back loop (:666-828)
+  reconcile_and_filter_flows  <-> ReconcileAndFilterFlows.process (:386-493):
+                                  clean, upsample the coarser flows onto the
+                                  base lattice (`map_utils.resample_map`),
+                                  reconcile
 
 `EstimateMissingFlow` takes a 2-channel flow of a fixed look-back and tries to
 fill the vectors that are NaN by correlating the section against earlier ones,
@@ -23,13 +27,13 @@ two kernels of their own (`sfm_flow_select`, `sfm_missing_flow_update`) around
 the correlation `flow_field()` runs.  Per round the host reads one integer.
 
 Not covered: volume stores, mask configs, Beam counters and timers, image /
-mask caches, `ReconcileAndFilterFlows` (its upsampling goes through
-`resample_map`), 3-D flows, targeting fields, and batching several sections'
+mask caches, 3-D flows, targeting fields, and batching several sections'
 rounds into one correlation launch -- every (section, look-back) stays one
 call, as in the reference, because the patches of a batch are coupled.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import dataclasses
 from typing import Any
@@ -286,6 +290,157 @@ def missing_flow_update(field, out_planes, mask, attempts, filled_ptr: int, *,
   d.filled = filled_ptr
   d.stream = _dev.stream_ptr()
   _abi.check(_abi.load().sfm_missing_flow_update(C.byref(d)))
+
+
+@dataclasses.dataclass(frozen=True)
+class CoarseFlow:
+  """One of the lower-resolution flows of `reconcile_and_filter_flows`."""
+  flow: Any                          # [c, z, y, x] over `box`
+  box: Any                           # its read box: `.start` / `.size` or a (start, size) pair, xyz
+  scale: float                       # base pixel size / this flow's pixel size, <= 1
+  mag_scale: float | None = None     # divisor of the vectors; None: `scale`
+
+
+_Box = collections.namedtuple('_Box', 'start size')
+
+
+def _xyz_box(box) -> _Box:
+  start, size = ((box.start, box.size) if hasattr(box, 'start') else box)
+  return _Box(tuple(int(v) for v in np.asarray(start).ravel()),
+              tuple(int(v) for v in np.asarray(size).ravel()))
+
+
+def nearest_nodes(n: int, start: int, scale: float, q_start: int, q_n: int):
+  """Along one axis, the coarse node that `RegularGridInterpolator(method=
+  'nearest', bounds_error=False)` reads for the fine queries `q_start ..
+  q_start + q_n - 1` when the coarse nodes lie at `(start + k) / scale`
+  (processor/flow.py:447-461): the cell is found by bisection, the nearer end
+  is taken and a query halfway goes to the lower index.  Returns (index [q_n]
+  int64, outside [q_n] bool); `outside` marks the queries beyond the first or
+  last coarse node, which the interpolator answers with NaN.  Host only.
+  """
+  grid = (np.arange(n) + start) / scale
+  x = (np.arange(q_n) + q_start).astype(np.float64)
+  if n == 1:
+    return np.zeros(q_n, np.int64), x != grid[0]
+  i = np.clip(np.searchsorted(grid, x, side='right') - 1, 0, n - 2)
+  dist = (x - grid[i]) / (grid[i + 1] - grid[i])
+  return np.where(dist <= .5, i, i + 1).astype(np.int64), (x < grid[0]) | (x > grid[-1])
+
+
+def _clean_all_channels(flow, dev, min_peak_ratio, min_peak_sharpness, max_magnitude,
+                        max_deviation):
+  """`clean_flow` as the reference returns it: a 3-channel flow keeps its third
+  channel, NaN where a vector was rejected (flow_utils.py:65-67, 77)."""
+  import torch
+  from . import _dev
+  clean = flow_utils.clean_flow(flow, min_peak_ratio, min_peak_sharpness, max_magnitude,
+                                max_deviation).tensor
+  if tuple(flow.shape)[0] != 3:
+    return clean
+  raw = _dev.as_device_f32(flow, dev, copy=False)
+  # rejected: NaN now and not before (a vector with a NaN component fails no test)
+  bad = torch.isnan(clean[0]) & ~torch.isnan(raw[0])
+  third = torch.where(bad, torch.full_like(raw[2], float('nan')), raw[2])
+  return torch.cat([clean, third[None]])
+
+
+def reconcile_and_filter_flows(flow, box, coarse=(), *, min_peak_ratio: float,
+                               min_peak_sharpness: float, max_magnitude: float,
+                               max_deviation: float, max_gradient: float,
+                               min_patch_size: int, multi_section: bool = False,
+                               base_delta_z: int = 0, mask=None):
+  """The compute of `ReconcileAndFilterFlows.process` (processor/flow.py:386-493)
+  on resident data: cleans a base flow and any number of coarser flows,
+  upsamples the coarser ones onto the base lattice and reconciles them.
+
+  flow: the base flow [c, z, y, x] (c = 2 .. 4) over `box` (`.start` / `.size`
+  or a (start, size) pair, xyz; only x and y are used).  coarse: `CoarseFlow`s
+  in order of decreasing preference, each with its read box in its own
+  coordinates, its `scale` <= 1 and an optional `mag_scale`.  mask: optional
+  bool, [z, y, x] or broadcastable to it, True = excluded.  Arrays are NumPy,
+  torch or DeviceArray; none is modified.
+
+  1. every flow goes through `clean_flow` with the four clean thresholds;
+  2. the base flow, and a coarse flow of scale 1, gets the `multi_section`
+     rule (:433-439): a flow without a third channel gets one that holds
+     `base_delta_z` where channel 0 is finite and NaN elsewhere;
+  3. a coarser flow is upsampled: all its z slices go through one
+     `map_utils.resample_map(flow[:2], read box, box, 1 / scale, 1)` call and
+     are divided by `mag_scale`; a fine node is NaN where its nearest coarse
+     node (`nearest_nodes`) is NaN in channel 0 or the node lies outside the
+     coarse grid; with `multi_section` channel 2 is the nearest coarse node's;
+     a third channel of the base flow without `multi_section` is 0, as in the
+     reference; `mask` is applied to the upsampled flows only;
+  4. `flow_utils.reconcile_flows` with `max_gradient`, `max_deviation` and
+     `min_patch_size`.
+
+  The flows stay on the device throughout; the host waits for it once per
+  coarser flow, where `resample_map` reads the per-slice status of its
+  triangulation (a refused slice raises SofimaAmdError there).
+
+  Returns a [2 or 3, z, y, x] float32 DeviceArray.  The upsampled values carry
+  `resample_map`'s contract: equal to the reference's where all Delaunay
+  triangulations of the valid coarse nodes agree, one admissible value
+  elsewhere.
+  """
+  import torch
+  from . import _dev, map_utils
+  dev = _dev.device()
+  box = _xyz_box(box)
+  thresholds = (min_peak_ratio, min_peak_sharpness, max_magnitude, max_deviation)
+
+  def expand(f):      # the multi_section rule
+    if not multi_section or f.shape[0] == 3:
+      return f
+    third = torch.full_like(f[0], float('nan'))
+    third[torch.isfinite(f[0])] = float(base_delta_z)
+    return torch.cat([f[:2], third[None]])
+
+  base = expand(_clean_all_channels(flow, dev, *thresholds))
+  nz, ny, nx = (int(v) for v in base.shape[1:])
+  if (nx, ny) != box.size[:2]:
+    raise ValueError(f'box size {box.size} mismatch with the base flow {tuple(base.shape)}')
+  mask_d = _dev.as_device_mask(mask, dev)
+  if mask_d is not None:
+    mask_d = torch.broadcast_to(mask_d.bool(), (nz, ny, nx))
+  channels = 3 if multi_section else 2      # the reference's num_channels()
+  flows = [base]
+  for k, c in enumerate(coarse):
+    if not c.scale <= 1.0:
+      raise ValueError(f'coarse flow {k}: scale {c.scale} > 1')
+    f = _clean_all_channels(c.flow, dev, *thresholds)
+    if c.scale == 1:
+      f = expand(f)
+      if tuple(f.shape) != tuple(base.shape):
+        raise ValueError(f'coarse flow {k} of scale 1 must have the base shape')
+      flows.append(f)
+      continue
+    read_box = _xyz_box(c.box)
+    if f.shape[1] != nz or (int(f.shape[3]), int(f.shape[2])) != read_box.size[:2]:
+      raise ValueError(f'coarse flow {k}: shape {tuple(f.shape)} against read box '
+                       f'{read_box.size} and {nz} sections')
+    if f.shape[0] < channels:
+      raise ValueError(f'coarse flow {k} has no channel 2 for a multi-section result')
+    mag_scale = c.scale if c.mag_scale is None else c.mag_scale
+    hires = torch.zeros_like(base)
+    up = map_utils.resample_map(_dev.DeviceArray(f[:2].contiguous()), read_box, box,
+                                1 / c.scale, 1).tensor
+    iy, out_y = nearest_nodes(read_box.size[1], read_box.start[1], c.scale, box.start[1], ny)
+    ix, out_x = nearest_nodes(read_box.size[0], read_box.start[0], c.scale, box.start[0], nx)
+    near = f[:, :, torch.from_numpy(iy).to(dev)][:, :, :, torch.from_numpy(ix).to(dev)]
+    outside = torch.from_numpy(out_y[:, None] | out_x[None, :]).to(dev)
+    nan = torch.full((), float('nan'), dtype=torch.float32, device=dev)
+    invalid = torch.isnan(near[0]) | outside
+    # (a 0-dim device divisor: a true float32 division, as NumPy's)
+    hires[:2] = torch.where(
+        invalid, nan, up / torch.tensor(mag_scale, dtype=torch.float32, device=dev))
+    for ch in range(2, channels):
+      hires[ch] = torch.where(outside, nan, near[ch])
+    if mask_d is not None:
+      hires = torch.where(mask_d, nan, hires)
+    flows.append(hires)
+  return flow_utils.reconcile_flows(flows, max_gradient, max_deviation, min_patch_size)
 
 
 def search_deltas(delta_z: int, max_delta_z: int) -> list[int]:
