@@ -54,7 +54,9 @@ extern "C" {
                                    and sfm_fill_missing_nearest with
                                    sfm_fill_missing_nearest_workspace_bytes, and
                                    sfm_resample_map with
-                                   sfm_resample_map_workspace_bytes */
+                                   sfm_resample_map_workspace_bytes, and
+                                   sfm_compose_maps_tri with
+                                   sfm_compose_maps_tri_workspace_bytes */
 
 #define SFM_OK 0
 #define SFM_ERR_INVALID (-1)     /* bad argument / unsupported combination */
@@ -581,6 +583,53 @@ size_t sfm_resample_map_workspace_bytes(const SfmResampleMapDesc* desc);
  * coord_map; may be NULL when the output lattice is empty (status is still
  * written).  Asynchronous: read status after the stream has finished. */
 int sfm_resample_map(const SfmResampleMapDesc* desc, void* out);
+
+/* ------------------------------------------------------------------------
+ * Composition of two in-plane coordinate maps through a triangulation, the
+ * step of the cross-block reconcile.  Replaces map_utils.compose_maps
+ * (map_utils.py:549-611) on the engine of sfm_invert_map (sfm_compose_maps is
+ * the lattice sampler of compose_maps_fast).  Per z slice the nodes of map2
+ * where both channels of its absolute form are finite, at
+ * ((j + start2_x) * stride2, (i + start2_y) * stride2), are triangulated as in
+ * sfm_resample_map.  Node (w, u) of map1 asks at its absolute position
+ * T1(rel + (u * stride1 + start1_x * stride1)) (same for y); a node with a
+ * channel that is not finite gives NaN in both outputs.  A query is answered
+ * by the lowest-keyed triangle whose closed exact test contains it (lattice
+ * triangles first), so shared edges and vertices are deterministic.  The
+ * values are map2's absolute form T2(rel [* T2(scale2[z])] + (j * stride2 +
+ * start2_x * stride2)), interpolated in double; the result is rounded to T1
+ * and then made relative in T1: T1(double(r) - (u * stride1 + start1_x *
+ * stride1)).  T1 / T2 are float or double (f64_1 / f64_2).  map2 may have one
+ * z slice that serves every slice of map1: it is triangulated once, and
+ * scale2 (validity does not look at it) gives each slice of map1 its own
+ * factor.  Queries outside the convex hull, slices with fewer than 3 valid or
+ * only collinear nodes: NaN.  status[z2] and the limits are those of
+ * sfm_invert_map (SFM_INVMAP_*), per slice of map2.
+ * ---------------------------------------------------------------------- */
+typedef struct SfmComposeTriDesc {
+  int32_t shape1[3];            /* z, y, x of map1 and of out                */
+  int32_t shape2[3];            /* z, y, x of map2; z is 1 or shape1[0]      */
+  int32_t start1[2];            /* y, x of box1.start                        */
+  int32_t start2[2];            /* y, x of box2.start                        */
+  double stride1;               /* finite and > 0                            */
+  double stride2;               /* finite and > 0                            */
+  int32_t f64_1;                /* map1 and out are double, else float       */
+  int32_t f64_2;                /* map2 is double, else float                */
+  const void* map1;             /* device [2, z, y, x], relative format      */
+  const void* map2;             /* device [2, z or 1, y2, x2], relative      */
+  const double* scale2;         /* device [shape1[0]] or NULL                */
+  int32_t* status;              /* device [shape2[0]], caller-owned, written */
+  void* workspace;              /* sfm_compose_maps_tri_workspace_bytes()    */
+  size_t workspace_bytes;
+  void* stream;
+} SfmComposeTriDesc;
+
+/* Host arithmetic only (callable without a GPU); 0 for a NULL descriptor or
+ * an empty shape. */
+size_t sfm_compose_maps_tri_workspace_bytes(const SfmComposeTriDesc* desc);
+/* out: device [2, z, y, x] of map1's shape and type; must not overlap the
+ * maps.  Asynchronous: read status after the stream has finished. */
+int sfm_compose_maps_tri(const SfmComposeTriDesc* desc, void* out);
 
 /* ------------------------------------------------------------------------
  * Fold / stretch detection on a relaxed mesh, the step after relaxation.

@@ -190,6 +190,26 @@ class SfmResampleMapDesc(C.Structure):
   ]
 
 
+class SfmComposeTriDesc(C.Structure):
+  _fields_ = [
+      ('shape1', i32 * 3),
+      ('shape2', i32 * 3),
+      ('start1', i32 * 2),
+      ('start2', i32 * 2),
+      ('stride1', C.c_double),
+      ('stride2', C.c_double),
+      ('f64_1', i32),
+      ('f64_2', i32),
+      ('map1', C.c_void_p),
+      ('map2', C.c_void_p),
+      ('scale2', C.c_void_p),
+      ('status', C.c_void_p),
+      ('workspace', C.c_void_p),
+      ('workspace_bytes', C.c_size_t),
+      ('stream', C.c_void_p),
+  ]
+
+
 class SfmMaskIrregularDesc(C.Structure):
   _fields_ = [
       ('shape', i32 * 2),
@@ -697,6 +717,8 @@ SIGNATURES = {
     'sfm_invert_map': (C.c_int, [C.POINTER(SfmInvertMapDesc), C.c_void_p]),
     'sfm_resample_map_workspace_bytes': (C.c_size_t, [C.POINTER(SfmResampleMapDesc)]),
     'sfm_resample_map': (C.c_int, [C.POINTER(SfmResampleMapDesc), C.c_void_p]),
+    'sfm_compose_maps_tri_workspace_bytes': (C.c_size_t, [C.POINTER(SfmComposeTriDesc)]),
+    'sfm_compose_maps_tri': (C.c_int, [C.POINTER(SfmComposeTriDesc), C.c_void_p]),
     'sfm_mask_irregular': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,
                                      C.c_void_p]),
     'sfm_mask_irregular_f64': (C.c_int, [C.POINTER(SfmMaskIrregularDesc), C.c_void_p,

@@ -2,6 +2,7 @@
 //
 //   sfm_invert_map    <->  map_utils.invert_map, 2-D branch (map_utils.py:392-463)
 //   sfm_resample_map  <->  map_utils.resample_map, linear (map_utils.py:490-546)
+//   sfm_compose_maps_tri  <->  map_utils.compose_maps (map_utils.py:549-611)
 //
 // The reference triangulates the absolute positions of the valid nodes of a z
 // slice with Qhull and interpolates the source lattice coordinates linearly
@@ -49,8 +50,20 @@
 //              ((u + start) * dst_stride); values: the two channels of the map
 //              itself, stored in the map's type
 //
-// In kResample every full quad is an exact square: the in-circle test ties and
-// the perturbation (lowest node id first: corner a of the quad) gives
+//   kCompose   points: the lattice of map2 ((j + start) * stride2) at the nodes
+//              where both channels of abs_map2 are finite; queries: the
+//              absolute positions of map1's nodes, arbitrary points, so steps
+//              5 and 6 are kernels of their own (cp_*): a query-major point
+//              location in the lattice part R (the cell guessed from the
+//              query and its eight neighbours, exact closed tests, lowest key
+//              first), a triangle-major pass over the queries that R left
+//              over, and a gather of abs_map2 that is made relative in map1's
+//              type.  The winner of a query is the one the scatter would
+//              pick: the lowest-keyed triangle whose closed exact test
+//              contains it.
+//
+// In kResample and kCompose every full quad is an exact square: the in-circle
+// test ties and the perturbation (lowest node id first: corner a of the quad) gives
 // orient(b, c, d) > 0, so the diagonal is always b-d, from (i, j + 1) to
 // (i + 1, j).  No quad can fold there.
 #include "sfm_common.h"
@@ -95,7 +108,7 @@ struct SliceInfo {
   int qcount;      // triangles that contain the probe point
 };
 
-enum Mode : int { kInvert = 0, kResample = 1 };
+enum Mode : int { kInvert = 0, kResample = 1, kCompose = 2 };
 
 struct Args {
   const void* map;    // [2, Z, H, W]: double (kInvert), float or double (kResample)
@@ -121,6 +134,14 @@ struct Args {
   void* out;          // [2, Z, Hd, Wd], of the map's type
   int capB, capT, capQ;
   unsigned capE, capTH;
+  // kCompose only
+  const void* map1;     // [2, Zq, Hd, Wd]: the queries; Z is 1 or Zq
+  int Zq;
+  const double* scale2;  // [Zq] or NULL: factor of map2's relative values
+  longlong2* cq;        // [Zq, Hd, Wd] queries on the predicate grid
+  int* lcount;          // [Zq] queries that no triangle of R contains
+  int* llist;           // [Zq, Hd * Wd] their indices in the slice
+  int4* ibox;           // [Z] (-min j, max j, -min i, max i) of the valid nodes
 };
 
 // ---------------------------------------------------------------- predicates
@@ -363,8 +384,16 @@ __global__ void __launch_bounds__(kBlock) im_prep_kernel(Args a) {
         p.y = ry + ((double)i * a.sy + (double)a.sy0 * a.sy);
       }
     } else {
-      // the reference looks at channel 0 only; the integer sum, then one product
-      valid = isfinite(map[t]);
+      if constexpr (MODE == kResample) {
+        // the reference looks at channel 0 only
+        valid = isfinite(map[t]);
+      } else {
+        // both channels of abs_map2, rounded to the map's type
+        const T ax = (T)((double)map[t] + ((double)j * a.sx + (double)a.sx0 * a.sx));
+        const T ay = (T)((double)map[n + t] + ((double)i * a.sy + (double)a.sy0 * a.sy));
+        valid = isfinite(ax) && isfinite(ay);
+      }
+      // the integer sum, then one product
       p.x = (double)((long long)j + a.sx0) * a.sx;
       p.y = (double)((long long)i + a.sy0) * a.sy;
     }
@@ -379,6 +408,15 @@ __global__ void __launch_bounds__(kBlock) im_prep_kernel(Args a) {
     }
     a.pos[t] = p;
     a.bid[t] = -1;
+    if constexpr (MODE == kCompose) {
+      if (cnt) {
+        // the box only grows: a stale read costs an atomic, never a node
+        int* b = &a.ibox[z].x;
+        const int c[4] = {-j, j, -i, i};
+        for (int m = 0; m < 4; ++m)
+          if (__atomic_load_n(&b[m], __ATOMIC_RELAXED) < c[m]) atomicMax(&b[m], c[m]);
+      }
+    }
   }
   if (wave_one_slice(z)) {
     for (int off = 32; off > 0; off >>= 1) {
@@ -961,6 +999,207 @@ __global__ void __launch_bounds__(kBlock) im_gather_kernel(Args a) {
   out[n + (long long)z * per + r] = (T)oy;
 }
 
+// ------------------------------------------------ kCompose: arbitrary queries
+
+// The slice of map2 that answers slice z of map1 (one slice serves them all).
+__device__ __forceinline__ int compose_z2(const Args& a, int z) { return a.Z == 1 ? 0 : z; }
+
+// Node (w, u) of map1 (element t of a channel) in absolute format, rounded to
+// map1's type as to_absolute stores it; false when a channel is not finite.
+template <typename T1>
+__device__ __forceinline__ bool compose_query(const Args& a, long long t, int w, int u,
+                                              double* qx, double* qy) {
+  const T1* m1 = static_cast<const T1*>(a.map1);
+  const long long n1 = (long long)a.Zq * a.Hd * a.Wd;
+  const T1 ax = (T1)((double)m1[t] + ((double)u * a.qs + (double)a.qx0 * a.qs));
+  const T1 ay = (T1)((double)m1[n1 + t] + ((double)w * a.qs + (double)a.qy0 * a.qs));
+  *qx = (double)ax;
+  *qy = (double)ay;
+  return isfinite(ax) && isfinite(ay);
+}
+
+__device__ __forceinline__ void tri_points(const Args& a, long long base, const int* v,
+                                           ll P[3][2]) {
+  for (int m = 0; m < 3; ++m) {
+    const longlong2 q = a.qpos[base + v[m]];
+    P[m][0] = q.x;
+    P[m][1] = q.y;
+  }
+}
+
+__device__ __forceinline__ bool tri_contains(const ll P[3][2], ll X, ll Y) {
+  bool in = true;
+  for (int m = 0; m < 3 && in; ++m)
+    in = orient(P[m][0], P[m][1], P[(m + 1) % 3][0], P[(m + 1) % 3][1], X, Y) >= 0;
+  return in;
+}
+
+// One thread per node of map1: the query on the predicate grid, then the
+// triangles of R in the guessed cell of map2 and its eight neighbours in key
+// order (the guess may be off by one, and a query on a lattice vertex lies in
+// four cells: the exact tests decide).  A query that R does not contain and
+// that lies in the bounding box of the valid nodes goes on the slice's
+// leftover list for cp_scatter_o_kernel.
+template <typename T1>
+__global__ void __launch_bounds__(kBlock) cp_locate_kernel(Args a) {
+  const long long per = (long long)a.Hd * a.Wd;
+  const long long t = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (t >= (long long)a.Zq * per) return;
+  const int z = (int)(t / per), r = (int)(t % per);
+  const int w = r / a.Wd, u = r % a.Wd;
+  const int z2 = compose_z2(a, z);
+  const SliceInfo s = a.info[z2];
+  double qx, qy;
+  if (s.nvalid < 3 || !compose_query<T1>(a, t, w, u, &qx, &qy)) return;
+  const int g = slice_g(s);
+  const double lim = 2305843009213693952.0;  // 2^61
+  const double fx = ldexp(qx, g), fy = ldexp(qy, g);
+  if (!(fabs(fx) < lim && fabs(fy) < lim)) return;
+  const ll X = llrint(fx), Y = llrint(fy);
+  const int4 b = a.ibox[z2];
+  if (X < quant((double)((ll)-b.x + a.sx0) * a.sx, g) ||
+      X > quant((double)((ll)b.y + a.sx0) * a.sx, g) ||
+      Y < quant((double)((ll)-b.z + a.sy0) * a.sy, g) ||
+      Y > quant((double)((ll)b.w + a.sy0) * a.sy, g))
+    return;
+  longlong2 c;
+  c.x = X;
+  c.y = Y;
+  a.cq[t] = c;
+  const int H = a.H, W = a.W;
+  // inside the box: the quotients are within the lattice's index range
+  const int cj = (int)(floor(qx / a.sx) - (double)a.sx0);
+  const int ci = (int)(floor(qy / a.sy) - (double)a.sy0);
+  const unsigned char* split = a.split + (long long)z2 * (H - 1) * (W - 1);
+  const long long base = (long long)z2 * H * W;
+  for (int di = -1; di <= 1; ++di)
+    for (int dj = -1; dj <= 1; ++dj) {
+      const int qi = ci + di, qj = cj + dj;
+      if (qi < 0 || qj < 0 || qi >= H - 1 || qj >= W - 1) continue;
+      const int q = qi * (W - 1) + qj;
+      const int sp = split[q];
+      if (sp == 0) continue;
+      for (int h = 0; h < 2; ++h) {
+        int k[3], v[3];
+        quad_tri(sp, h, k);
+        for (int m = 0; m < 3; ++m) v[m] = corner(W, qi, qj, k[m]);
+        ll P[3][2];
+        tri_points(a, base, v, P);
+        if (tri_contains(P, X, Y)) {
+          a.qkeys[t] = (unsigned long long)q << 1 | h;
+          return;
+        }
+      }
+    }
+  const int k = atomicAdd(&a.lcount[z], 1);
+  a.llist[(long long)z * per + k] = r;
+}
+
+// One wave per triangle outside R; the lanes stride over the leftover list of
+// the slice.  The bounding-box reject is taken on the predicate grid, where it
+// is exact; the lowest key wins a query, as in the scatter.
+__global__ void __launch_bounds__(kBlock) cp_scatter_o_kernel(Args a) {
+  const long long per = (long long)a.Hd * a.Wd;
+  const int lane = threadIdx.x & 63;
+  const int nw = gridDim.x * (kBlock / 64);
+  for (int z = blockIdx.y; z < a.Zq; z += gridDim.y) {
+    const int z2 = compose_z2(a, z);
+    const int n = a.info[z2].ntri;
+    const int nl = a.lcount[z];
+    if (nl == 0) continue;
+    const long long base = (long long)z2 * a.H * a.W;
+    const int* list = a.llist + (long long)z * per;
+    const longlong2* cq = a.cq + (long long)z * per;
+    unsigned long long* keys = a.qkeys + (long long)z * per;
+    for (int t = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); t < n; t += nw) {
+      const int4 tr = a.tris[(long long)z2 * a.capT + t];
+      const int v[3] = {tr.x, tr.y, tr.z};
+      const unsigned long long key = 1ull << 63 | (unsigned long long)tr.x << (2 * kNodeBits) |
+                                     (unsigned long long)tr.y << kNodeBits |
+                                     (unsigned long long)tr.z;
+      ll P[3][2];
+      tri_points(a, base, v, P);
+      ll mnx = P[0][0], mxx = P[0][0], mny = P[0][1], mxy = P[0][1];
+      for (int m = 1; m < 3; ++m) {
+        mnx = P[m][0] < mnx ? P[m][0] : mnx;
+        mxx = P[m][0] > mxx ? P[m][0] : mxx;
+        mny = P[m][1] < mny ? P[m][1] : mny;
+        mxy = P[m][1] > mxy ? P[m][1] : mxy;
+      }
+      for (int c = lane; c < nl; c += 64) {
+        const int r = list[c];
+        const longlong2 q = cq[r];
+        if (q.x < mnx || q.x > mxx || q.y < mny || q.y > mxy) continue;
+        if (tri_contains(P, q.x, q.y)) atomicMin(&keys[r], key);
+      }
+    }
+  }
+}
+
+// The barycentric value of abs_map2 (rel * scale in map2's type, made absolute
+// and rounded to map2's type) over the winning triangle, stored as the
+// reference stores it: rounded to map1's type, then made relative in it.
+template <typename T1, typename T2>
+__global__ void __launch_bounds__(kBlock) cp_gather_kernel(Args a) {
+  const long long per = (long long)a.Hd * a.Wd;
+  const long long n = (long long)a.Zq * per;
+  const long long t = blockIdx.x * (long long)kBlock + threadIdx.x;
+  if (t >= n) return;
+  const int z = (int)(t / per), r = (int)(t % per);
+  const int w = r / a.Wd, u = r % a.Wd;
+  const int z2 = compose_z2(a, z);
+  const unsigned long long key = a.qkeys[t];
+  double ox = __builtin_nan(""), oy = __builtin_nan("");
+  if (key != kEmptyKey) {
+    int v[3];
+    if (key >> 63) {
+      const unsigned long long m = (1ull << kNodeBits) - 1;
+      v[0] = (int)(key >> (2 * kNodeBits) & m);
+      v[1] = (int)(key >> kNodeBits & m);
+      v[2] = (int)(key & m);
+    } else {
+      const int q = (int)(key >> 1), h = (int)(key & 1);
+      const int i = q / (a.W - 1), j = q % (a.W - 1);
+      int k[3];
+      quad_tri(a.split[(long long)z2 * (a.H - 1) * (a.W - 1) + q], h, k);
+      for (int m = 0; m < 3; ++m) v[m] = corner(a.W, i, j, k[m]);
+    }
+    const long long base = (long long)z2 * a.H * a.W;
+    const long long n2 = (long long)a.Z * a.H * a.W;
+    const T2* map2 = static_cast<const T2*>(a.map);
+    double2 p[3];
+    double vx[3], vy[3];
+    for (int m = 0; m < 3; ++m) {
+      p[m] = a.pos[base + v[m]];
+      const int i = v[m] / a.W, j = v[m] % a.W;
+      T2 rx = map2[base + v[m]], ry = map2[n2 + base + v[m]];
+      if (a.scale2) {
+        const T2 sc = (T2)a.scale2[z];
+        rx = rx * sc;
+        ry = ry * sc;
+      }
+      vx[m] = (double)(T2)((double)rx + ((double)j * a.sx + (double)a.sx0 * a.sx));
+      vy[m] = (double)(T2)((double)ry + ((double)i * a.sy + (double)a.sy0 * a.sy));
+    }
+    double qx, qy;
+    compose_query<T1>(a, t, w, u, &qx, &qy);
+    const double e1x = p[1].x - p[0].x, e1y = p[1].y - p[0].y;
+    const double e2x = p[2].x - p[0].x, e2y = p[2].y - p[0].y;
+    const double dx = qx - p[0].x, dy = qy - p[0].y;
+    const double det = e1x * e2y - e1y * e2x;
+    const double l1 = (dx * e2y - dy * e2x) / det;
+    const double l2 = (e1x * dy - e1y * dx) / det;
+    const double l0 = 1.0 - l1 - l2;
+    ox = l0 * vx[0] + l1 * vx[1] + l2 * vx[2];
+    oy = l0 * vy[0] + l1 * vy[1] + l2 * vy[2];
+  }
+  // ret[valid] = u (rounds to map1's type), then to_relative in that type
+  const T1 rx = (T1)ox, ry = (T1)oy;
+  T1* out = static_cast<T1*>(a.out);
+  out[t] = (T1)((double)rx - ((double)u * a.qs + (double)a.qx0 * a.qs));
+  out[n + t] = (T1)((double)ry - ((double)w * a.qs + (double)a.qy0 * a.qs));
+}
+
 unsigned pow2_at_least(unsigned long long v) {
   unsigned long long p = 1;
   while (p < v) p <<= 1;
@@ -1029,11 +1268,11 @@ int check_shapes(const char* name, const int32_t* shape, const int32_t* dst_shap
   return SFM_OK;
 }
 
-// Binds the workspace and runs the engine in one mode on a map of type T.
-// `a` carries the map, the lattices, the status and the output.
+// Binds the workspace and runs steps 1 to 4 (the verified triangulation) in one
+// mode on a map of type T; `queries` keys are cleared for step 5.
 template <int MODE, typename T>
-int run(Args a, const int32_t* shape, const int32_t* dst_shape, const InvLayout& w,
-        void* workspace, hipStream_t st) {
+int triangulate(Args& a, const int32_t* shape, const int32_t* dst_shape, long long queries,
+                const InvLayout& w, void* workspace, hipStream_t st) {
   char* ws = static_cast<char*>(workspace);
   a.Z = shape[0];
   a.H = shape[1];
@@ -1053,7 +1292,7 @@ int run(Args a, const int32_t* shape, const int32_t* dst_shape, const InvLayout&
   a.evals = reinterpret_cast<int*>(ws + w.evals);
   a.tkeys = reinterpret_cast<unsigned long long*>(ws + w.tkeys);
   a.queue = reinterpret_cast<unsigned*>(ws + w.queue);
-  a.qkeys = reinterpret_cast<unsigned long long*>(ws + w.qkeys);
+  if constexpr (MODE != kCompose) a.qkeys = reinterpret_cast<unsigned long long*>(ws + w.qkeys);
   a.capB = w.capB;
   a.capT = w.capT;
   a.capQ = w.capQ;
@@ -1062,7 +1301,6 @@ int run(Args a, const int32_t* shape, const int32_t* dst_shape, const InvLayout&
   const long long Z = a.Z;
   const long long nodes = Z * hw;
   const long long quads = Z * (a.H - 1) * (long long)(a.W - 1);
-  const long long queries = Z * a.Hd * (long long)a.Wd;
   SFM_HIP_CHECK(hipMemsetAsync(a.status, 0, Z * sizeof(int), st));
   SFM_HIP_CHECK(hipMemsetAsync(a.used, 0, nodes, st));
   SFM_HIP_CHECK(hipMemsetAsync(a.ekeys, 0, Z * w.capE * sizeof(unsigned), st));
@@ -1082,16 +1320,96 @@ int run(Args a, const int32_t* shape, const int32_t* dst_shape, const InvLayout&
   hipLaunchKernelGGL(im_verify_o_kernel, dim3(16, (unsigned)Z), dim3(kBlock), 0, st, a);
   hipLaunchKernelGGL(im_verify_nodes_kernel, dim3(blocks(nodes)), dim3(kBlock), 0, st, a);
   SFM_LAUNCH_CHECK();
+  return SFM_OK;
+}
+
+// Runs the engine over a query lattice (kInvert, kResample).  `a` carries the
+// map, the lattices, the status and the output.
+template <int MODE, typename T>
+int run(Args a, const int32_t* shape, const int32_t* dst_shape, const InvLayout& w,
+        void* workspace, hipStream_t st) {
+  const long long queries = (long long)shape[0] * dst_shape[0] * dst_shape[1];
+  if (const int err = triangulate<MODE, T>(a, shape, dst_shape, queries, w, workspace, st))
+    return err;
+  const long long quads = (long long)a.Z * (a.H - 1) * (long long)(a.W - 1);
   if (queries > 0) {
     if (quads > 0)
       hipLaunchKernelGGL(im_scatter_r_kernel<MODE>, dim3(blocks(quads)), dim3(kBlock), 0, st,
                          a);
-    hipLaunchKernelGGL(im_scatter_o_kernel<MODE>, dim3(64, (unsigned)Z), dim3(kBlock), 0, st,
+    hipLaunchKernelGGL(im_scatter_o_kernel<MODE>, dim3(64, (unsigned)a.Z), dim3(kBlock), 0, st,
                        a);
     hipLaunchKernelGGL((im_gather_kernel<MODE, T>), dim3(blocks(queries)), dim3(kBlock), 0, st,
                        a);
     SFM_LAUNCH_CHECK();
   }
+  return SFM_OK;
+}
+
+// kCompose: the triangulation's workspace (no query lattice), then the keys,
+// the quantized queries, the leftover lists and the boxes of the valid nodes.
+struct ComposeLayout {
+  InvLayout tri;
+  size_t qkeys, cq, lcount, llist, ibox, bytes;
+};
+
+ComposeLayout compose_layout(const int32_t* shape1, const int32_t* shape2) {
+  ComposeLayout c{};
+  const int32_t none[2] = {0, 0};
+  c.tri = invmap_layout(shape2, none);
+  const size_t Z1 = shape1[0], queries = Z1 * (size_t)shape1[1] * shape1[2];
+  size_t off = c.tri.bytes;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  c.qkeys = take(queries * sizeof(unsigned long long));
+  c.cq = take(queries * sizeof(longlong2));
+  c.lcount = take(Z1 * sizeof(int));
+  c.llist = take(queries * sizeof(int));
+  c.ibox = take((size_t)shape2[0] * sizeof(int4));
+  c.bytes = off;
+  return c;
+}
+
+// 0 when the shapes of a composition pass (both maps checked, z of map2 is 1 or
+// map1's).
+int check_compose(const SfmComposeTriDesc* d) {
+  const int32_t dst[2] = {d->shape1[1], d->shape1[2]};
+  for (int i = 0; i < 3; ++i)
+    if (d->shape1[i] < 1) return sfm::fail(SFM_ERR_INVALID, "compose_maps_tri: bad shape");
+  if (const int err = check_shapes("compose_maps_tri", d->shape2, dst, d->stride1, d->stride2))
+    return err;
+  if (d->shape2[0] != 1 && d->shape2[0] != d->shape1[0])
+    return sfm::fail(SFM_ERR_INVALID, "compose_maps_tri: map2 has %d z slices, map1 %d",
+                     d->shape2[0], d->shape1[0]);
+  if ((long long)d->shape1[0] * d->shape1[1] * d->shape1[2] > 0x7fffffffLL)
+    return sfm::fail(SFM_ERR_INVALID, "compose_maps_tri: more than 2^31 - 1 nodes");
+  return SFM_OK;
+}
+
+template <typename T1, typename T2>
+int run_compose(Args a, const SfmComposeTriDesc* d, const ComposeLayout& c, hipStream_t st) {
+  char* ws = static_cast<char*>(d->workspace);
+  const int32_t dst[2] = {d->shape1[1], d->shape1[2]};
+  const long long Z1 = d->shape1[0], queries = Z1 * dst[0] * dst[1];
+  a.Zq = (int)Z1;
+  a.qkeys = reinterpret_cast<unsigned long long*>(ws + c.qkeys);
+  a.cq = reinterpret_cast<longlong2*>(ws + c.cq);
+  a.lcount = reinterpret_cast<int*>(ws + c.lcount);
+  a.llist = reinterpret_cast<int*>(ws + c.llist);
+  a.ibox = reinterpret_cast<int4*>(ws + c.ibox);
+  SFM_HIP_CHECK(hipMemsetAsync(a.lcount, 0, Z1 * sizeof(int), st));
+  // 0x80808080 is below every -index and index
+  SFM_HIP_CHECK(hipMemsetAsync(a.ibox, 0x80, d->shape2[0] * sizeof(int4), st));
+  if (const int err =
+          triangulate<kCompose, T2>(a, d->shape2, dst, queries, c.tri, d->workspace, st))
+    return err;
+  hipLaunchKernelGGL(cp_locate_kernel<T1>, dim3(blocks(queries)), dim3(kBlock), 0, st, a);
+  const unsigned gy = (unsigned)(Z1 < 65535 ? Z1 : 65535);
+  hipLaunchKernelGGL(cp_scatter_o_kernel, dim3(64, gy), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((cp_gather_kernel<T1, T2>), dim3(blocks(queries)), dim3(kBlock), 0, st, a);
+  SFM_LAUNCH_CHECK();
   return SFM_OK;
 }
 
@@ -1162,4 +1480,39 @@ extern "C" int sfm_resample_map(const SfmResampleMapDesc* d, void* out) {
   if (d->f64)
     return run<kResample, double>(a, d->shape, d->dst_shape, w, d->workspace, st);
   return run<kResample, float>(a, d->shape, d->dst_shape, w, d->workspace, st);
+}
+
+extern "C" size_t sfm_compose_maps_tri_workspace_bytes(const SfmComposeTriDesc* d) {
+  if (!d) return 0;
+  for (int i = 0; i < 3; ++i)
+    if (d->shape1[i] < 1 || d->shape2[i] < 1) return 0;
+  return compose_layout(d->shape1, d->shape2).bytes;
+}
+
+extern "C" int sfm_compose_maps_tri(const SfmComposeTriDesc* d, void* out) {
+  if (!d || !d->map1 || !d->map2 || !d->status || !out)
+    return sfm::fail(SFM_ERR_INVALID, "compose_maps_tri: NULL argument");
+  if (const int err = check_compose(d)) return err;
+  const ComposeLayout c = compose_layout(d->shape1, d->shape2);
+  if (!d->workspace || d->workspace_bytes < c.bytes)
+    return sfm::fail(SFM_ERR_WORKSPACE, "compose_maps_tri workspace needs %zu bytes, got %zu",
+                     c.bytes, d->workspace_bytes);
+  Args a{};
+  a.map = d->map2;
+  a.sy0 = d->start2[0];
+  a.sx0 = d->start2[1];
+  a.sy = a.sx = d->stride2;
+  a.map1 = d->map1;
+  a.qy0 = d->start1[0];
+  a.qx0 = d->start1[1];
+  a.qs = d->stride1;
+  a.scale2 = d->scale2;
+  a.status = d->status;
+  a.out = out;
+  hipStream_t st = static_cast<hipStream_t>(d->stream);
+  if (d->f64_1)
+    return d->f64_2 ? run_compose<double, double>(a, d, c, st)
+                    : run_compose<double, float>(a, d, c, st);
+  return d->f64_2 ? run_compose<float, double>(a, d, c, st)
+                  : run_compose<float, float>(a, d, c, st);
 }

@@ -6,21 +6,22 @@ branch of `map_utils.invert_map` (:392-463) and the helpers that the
 reference's renderers call around them: `to_absolute` / `to_relative`
 (:150-224), `outer_box` (:307-342), `inner_box` (:345-389, maps without NaN),
 `make_affine_map` (:789-811), the nearest-node branch of `fill_missing`
-(:227-304 with `interpolate_first=False`) and the linear `resample_map`
-(:490-546).  The helpers are one pass over
+(:227-304 with `interpolate_first=False`), the linear `resample_map`
+(:490-546) and `compose_maps` (:549-611).  The helpers are one pass over
 memory each and take and return `DeviceArray`s, so a map produced by
 `invert_map` or `compose_maps_fast` is shifted or measured without a host
 round trip.  `invert_map` triangulates the deformed positions, so its Delaunay
 triangulation is unique and the device result has a parity contract.
 `resample_map`, `compose_maps` and the `interpolate_first=True` branch of
 `fill_missing` triangulate the regular lattice, where every quad is
-co-circular and Qhull picks the diagonals arbitrarily.  `resample_map` runs on
-the engine of `invert_map` under the contract that does exist there: the
-interpolant of one verified, deterministic Delaunay triangulation, equal to
-the reference wherever all Delaunay triangulations agree and one of the
-admissible values elsewhere (see its docstring).  `compose_maps` (arbitrary
-query points: point location) and the `interpolate_first=True` branch of
-`fill_missing` stay host geometry and out of scope (and with that branch,
+co-circular and Qhull picks the diagonals arbitrarily.  `resample_map` and
+`compose_maps` run on the engine of `invert_map` under the contract that does
+exist there: the interpolant of one verified, deterministic Delaunay
+triangulation, equal to the reference wherever all Delaunay triangulations
+agree and one of the admissible values elsewhere (see their docstrings);
+`compose_maps` asks at arbitrary points, which the engine locates in the
+triangulation with exact tests.  The `interpolate_first=True` branch of
+`fill_missing` stays host geometry and out of scope (and with that branch,
 `inner_box` of a map that holds NaN).
 `fill_missing(extrapolate=True, interpolate_first=False)` never touches Qhull:
 every invalid node takes the nearest valid node, an exact integer feature
@@ -305,7 +306,8 @@ def _engine_run(d, workspace_bytes, run, m, dst_size, dev):
 
 def _raise_refused(name, status):
   """Reads the per-slice status of the triangulation engine (the one host sync
-  of `invert_map` / `resample_map`) and raises for refused slices."""
+  of `invert_map` / `resample_map` / `compose_maps`) and raises for refused
+  slices."""
   st = status.cpu().numpy()
   bad = np.flatnonzero(st)
   if bad.size:
@@ -382,6 +384,101 @@ def _resample_launch(coord_map, src_box, dst_box, src_stride, dst_stride):
   lib = _abi.load()
   return _engine_run(d, lib.sfm_resample_map_workspace_bytes, lib.sfm_resample_map, m,
                      dst_size, dev)
+
+
+def compose_maps(map1, box1, stride1: float, map2, box2, stride2: float) -> DeviceArray:
+  """Composes two [2, z, y, x] coordinate maps: map2(map1(x, y)) over map1's nodes.
+
+  Same signature and box convention as the reference (map_utils.py:549-611):
+  both maps are in relative format, `box1` / `box2` have `.start` / `.size` in
+  xyz order (only x and y are used) and must agree with the maps.  Per z slice
+  the nodes of map2 where both channels of its absolute form are finite are
+  triangulated (Delaunay) at their lattice positions ((j + box2 start x) *
+  stride2, (i + box2 start y) * stride2), and map2's absolute form is
+  interpolated linearly in float64 at the absolute positions of map1's nodes;
+  the result is rounded to map1's dtype and made relative in it, as
+  `to_relative` does.  A node of map1 with NaN or inf in either channel is NaN
+  in both outputs, so are queries outside the convex hull of map2's valid
+  nodes and slices where map2 has fewer than 3 valid or only collinear nodes;
+  invalid nodes of map2 inside the hull are interpolated over.  The maps are
+  NumPy arrays, CUDA tensors or DeviceArrays, float32 or float64 in any
+  pairing; resident contiguous inputs are read where they lie and never
+  modified.  Returns a DeviceArray of map1's shape and dtype.
+
+  Contract (that of `resample_map`, carried to arbitrary queries).  The nodes
+  of map2 lie on a lattice, where Delaunay triangulations are not unique and
+  Qhull's choice is arbitrary.  The device interpolates over one verified,
+  deterministic Delaunay triangulation (a full quad is split from (i, j + 1) to
+  (i + 1, j); a query on a shared edge or vertex is answered by the
+  lowest-keyed triangle that contains it): the result equals the reference
+  wherever all Delaunay triangulations agree (an affine map2, holes included)
+  and is the interpolant over some Delaunay triangle that contains the query
+  everywhere else.
+
+  A slice of map2 with more than 7936 boundary nodes (valid nodes that are not
+  interior vertices of the full-quad lattice: a checkerboard of holes, not a
+  map with blob holes) raises SofimaAmdError naming the slice and the reason,
+  as in `invert_map`; it is never answered wrongly.  At most 2^21 nodes per
+  slice of map2.
+  """
+  if _map_shape(map1)[1:2] != _map_shape(map2)[1:2]:
+    raise ValueError(f'z mismatch: map1 {_map_shape(map1)}, map2 {_map_shape(map2)}')
+  out, status = _compose_launch(map1, box1, stride1, map2, box2, stride2)
+  _raise_refused('compose_maps', status)
+  return DeviceArray(out)
+
+
+def _compose_launch(map1, box1, stride1, map2, box2, stride2, scale2=None):
+  """`compose_maps` up to the status read: (out, status [z of map2] int32),
+  both device tensors.  Beyond the public call, map2 may have one z slice that
+  serves every slice of map1 (triangulated once), and `scale2` (a float64
+  device vector [z of map1]) multiplies map2's relative values in map2's
+  dtype, the reference's `offset * scale`."""
+  shape1, shape2 = _map_shape(map1), _map_shape(map2)
+  for name, shape in (('map1', shape1), ('map2', shape2)):
+    if len(shape) != 4 or shape[0] != 2:
+      raise ValueError(f'{name} must be [2, z, y, x], got shape {shape}')
+    if min(shape[1:]) < 1:
+      raise ValueError(f'empty {name}: {shape}')
+  if shape2[1] not in (1, shape1[1]):
+    raise ValueError(f'map2 has {shape2[1]} z slices, map1 {shape1[1]}')
+  stride1, stride2 = float(stride1), float(stride2)
+  for s in (stride1, stride2):
+    if not (np.isfinite(s) and s > 0):
+      raise ValueError(f'strides must be finite and positive, got {stride1}, {stride2}')
+  starts = []
+  for name, shape, b in (('box1', shape1, box1), ('box2', shape2, box2)):
+    start, size = _box_xy(b, name)
+    if (shape[3], shape[2]) != (size[0], size[1]):
+      raise ValueError(f'{name} shape ({size}) mismatch with coord map ({shape})')
+    starts.append(start)
+  dev = _dev.device()
+  m1 = _engine_map(map1, dev, keep_f32=True)
+  m2 = _engine_map(map2, dev, keep_f32=True)
+  d = _abi.SfmComposeTriDesc()
+  d.shape1 = (C.c_int32 * 3)(*m1.shape[1:])
+  d.shape2 = (C.c_int32 * 3)(*m2.shape[1:])
+  d.start1 = _i32_pair('box1.start', starts[0][1], starts[0][0])
+  d.start2 = _i32_pair('box2.start', starts[1][1], starts[1][0])
+  d.stride1, d.stride2 = stride1, stride2
+  d.f64_1 = int(m1.dtype == torch.float64)
+  d.f64_2 = int(m2.dtype == torch.float64)
+  d.map1, d.map2 = m1.data_ptr(), m2.data_ptr()
+  if scale2 is not None:
+    if not (scale2.is_cuda and scale2.dtype == torch.float64 and scale2.is_contiguous() and
+            tuple(scale2.shape) == (m1.shape[1],)):
+      raise ValueError('scale2 must be a contiguous float64 device vector [z of map1]')
+    d.scale2 = scale2.data_ptr()
+  status = torch.empty(int(m2.shape[1]), dtype=torch.int32, device=dev)
+  d.status = status.data_ptr()
+  lib = _abi.load()
+  ws = _dev.workspace(lib.sfm_compose_maps_tri_workspace_bytes(C.byref(d)), dev)
+  d.workspace = ws.data_ptr()
+  d.workspace_bytes = ws.numel()
+  d.stream = _dev.stream_ptr()
+  out = torch.empty_like(m1)
+  _abi.check(lib.sfm_compose_maps_tri(C.byref(d), out.data_ptr()))
+  return out, status
 
 
 # -- geometry helpers: to_absolute / to_relative / outer_box / inner_box /
