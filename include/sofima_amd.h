@@ -820,7 +820,7 @@ typedef struct SfmRenderTilesDesc {
 int sfm_render_tiles3d(const SfmRenderTilesDesc* desc);
 
 /* ------------------------------------------------------------------------
- * Spline orders 2 .. 5 of the two calls above (sfm_spline.hip, sfm_warp.hip).
+ * Spline orders 2 .. 5 of the two calls above (sfm_spline.hip, sfm_ndwarp_kernel.h).
  * SciPy samples orders above 1 from B-spline coefficients, not from the image:
  * scipy.ndimage.spline_filter(image, order, output=float64, mode="constant"),
  * a recursive filter along axis 0, then 1, then 2, each pass on the previous

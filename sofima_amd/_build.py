@@ -24,25 +24,62 @@ MFMA_UNITS = ('sfm_mfma_g10x11.hip', 'sfm_mfma_g20x11.hip', 'sfm_mfma_g15x11.hip
               'sfm_mfma_g5x6.hip', 'sfm_mfma_g4x5.hip', 'sfm_mfma_g3x4.hip',
               'sfm_xcorr_mfma.hip', 'sfm_mfma_host.hip')
 
-# Translation units and their extra flags, the slowest to compile first.  The mesh
-# kernels follow the reference's f32 operation order, so FMA contraction is disabled
-# there.
+# The units that hold the kernels of the map_coordinates family (csrc/sfm_ndwarp.h
+# lists them: one unit per spline order and dimension, the 3-D ones of orders 4 and 5
+# cut once more by map accessor).  Double arithmetic in SciPy's operation order: FMA
+# contraction is disabled in all of them, as in their host unit sfm_warp.hip.
+_NDWARP = ['-ffp-contract=off']
+NDWARP_UNITS = ('sfm_ndwarp_o0.hip', 'sfm_ndwarp_o2d2.hip', 'sfm_ndwarp_o2d3.hip',
+                'sfm_ndwarp_o3d2.hip', 'sfm_ndwarp_o3d3.hip', 'sfm_ndwarp_o4d2.hip',
+                'sfm_ndwarp_o4d3_abs.hip', 'sfm_ndwarp_o4d3_rel32.hip',
+                'sfm_ndwarp_o4d3_rel64.hip', 'sfm_ndwarp_o4d3_image.hip',
+                'sfm_ndwarp_o5d2.hip', 'sfm_ndwarp_o5d3_abs.hip', 'sfm_ndwarp_o5d3_rel32.hip',
+                'sfm_ndwarp_o5d3_rel64.hip', 'sfm_ndwarp_o5d3_image.hip')
+
+# Translation units and their extra flags, the slowest to compile first, as measured
+# one unit at a time (profiles/build_time.txt).  The mesh kernels follow the
+# reference's f32 operation order, so FMA contraction is disabled there.
 SOURCES = {
-    **{unit: _MFMA for unit in MFMA_UNITS},
-    'sfm_mesh.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MESH_FLAGS', '').split(),
-    'sfm_core.hip': [],
+    'sfm_ndwarp_o3d3.hip': _NDWARP,          # 61 s
+    'sfm_ndwarp_o2d3.hip': _NDWARP,
+    'sfm_ndwarp_o0.hip': _NDWARP,
+    'sfm_ndwarp_o4d3_abs.hip': _NDWARP,      # 24 s
+    'sfm_ndwarp_o5d3_rel32.hip': _NDWARP,
+    'sfm_ndwarp_o4d3_rel64.hip': _NDWARP,
+    'sfm_ndwarp_o5d3_rel64.hip': _NDWARP,
+    'sfm_ndwarp_o5d3_abs.hip': _NDWARP,
+    'sfm_ndwarp_o4d3_rel32.hip': _NDWARP,
+    'sfm_ndwarp_o5d2.hip': _NDWARP,
+    'sfm_mfma_g10x11.hip': _MFMA,            # 17 s
+    'sfm_ndwarp_o4d2.hip': _NDWARP,
+    'sfm_ndwarp_o3d2.hip': _NDWARP,
     'sfm_xcorr.hip': [],
-    'sfm_xcorr_fft.hip': [],
+    'sfm_ndwarp_o2d2.hip': _NDWARP,
+    'sfm_mfma_g6x7.hip': _MFMA,
+    'sfm_mfma_g8x9.hip': _MFMA,
+    'sfm_mfma_g7x8.hip': _MFMA,
+    'sfm_mesh.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MESH_FLAGS', '').split(),  # 10 s
+    'sfm_mfma_g5x6.hip': _MFMA,
+    'sfm_mfma_g4x5.hip': _MFMA,
+    'sfm_mfma_g3x4.hip': _MFMA,
+    'sfm_ndwarp_o5d3_image.hip': _NDWARP,
+    'sfm_ndwarp_o4d3_image.hip': _NDWARP,
+    'sfm_mfma_g20x11.hip': _MFMA,
+    'sfm_mfma_g15x11.hip': _MFMA,
+    'sfm_xcorr_mfma.hip': _MFMA,             # 5 s
     'sfm_fft_own.hip': [],
-    'sfm_maps.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MAPS_FLAGS', '').split(),
-    'sfm_flowutils.hip': ['-ffp-contract=off'],
-    'sfm_tileflows.hip': ['-ffp-contract=off'],
-    'sfm_invmap.hip': ['-ffp-contract=off'],
-    'sfm_comm.hip': [],
-    'sfm_warp.hip': ['-ffp-contract=off'],
     'sfm_spline.hip': ['-ffp-contract=off'],
+    'sfm_invmap.hip': ['-ffp-contract=off'],
+    'sfm_maps.hip': ['-ffp-contract=off'] + os.environ.get('SFM_MAPS_FLAGS', '').split(),
     'sfm_mapgeom.hip': ['-ffp-contract=off'],
+    'sfm_core.hip': [],
+    'sfm_flowutils.hip': ['-ffp-contract=off'],
     'sfm_fillmissing.hip': [],
+    'sfm_comm.hip': [],
+    'sfm_xcorr_fft.hip': [],
+    'sfm_mfma_host.hip': _MFMA,
+    'sfm_tileflows.hip': ['-ffp-contract=off'],
+    'sfm_warp.hip': ['-ffp-contract=off'],   # 2 s
 }
 # SFM_BUILD_FLAGS: extra flags for every unit (-DSFM_MEASUREMENT_SWITCHES: the library
 # honours the measurement-only switches, see csrc/sfm_common.h)

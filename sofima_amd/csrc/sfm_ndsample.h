@@ -1,5 +1,5 @@
 // scipy.ndimage.map_coordinates on the device, orders 0 to 5: the samplers shared
-// by the kernels of sfm_warp.hip.  Orders 0 and 1 read the image, orders 2 to 5
+// by the kernels of sfm_ndwarp_kernel.h.  Orders 0 and 1 read the image, orders 2 to 5
 // its float64 B-spline coefficients (sfm_spline.hip).  Double arithmetic in SciPy's
 // operation order; the units that include this are built with -ffp-contract=off.
 //

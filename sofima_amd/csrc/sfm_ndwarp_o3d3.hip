@@ -1,0 +1,4 @@
+// The nd-warp, affine and render kernels of spline order 3, 3-D.
+#include "sfm_ndwarp_kernel.h"
+
+SFM_NDWARP_UNIT(3, 3)

@@ -1,0 +1,4 @@
+// The nd-warp kernels of spline order 4, 3-D, that read the float64 absolute map.
+#include "sfm_ndwarp_kernel.h"
+
+SFM_NDWARP_MAP_UNIT(4, 3, AbsoluteMap)

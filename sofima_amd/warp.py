@@ -130,11 +130,7 @@ def _inter_tab(kind: int, fixed: bool) -> np.ndarray:
   return np.ascontiguousarray(it.astype(np.int16))
 
 
-def _box(b):
-  """(start xyz, size xyz) of a bounding box object or (start, size) pair."""
-  if hasattr(b, 'start') and hasattr(b, 'size'):
-    return np.asarray(b.start), np.asarray(b.size)
-  return np.asarray(b[0]), np.asarray(b[1])
+_box = map_utils._box
 
 
 def _make_contiguous(image: np.ndarray):
@@ -478,13 +474,8 @@ def ndimage_warp(image, coord_map, stride, work_size, overlap,
   d.image = img_t.data_ptr()
   d.out = out_t.data_ptr()
   d.stream = _dev.stream_ptr()
-  if order in _spline.ORDERS:
-    ishape = pad + tuple(image.shape)
-    coeffs, _ = _spline.prefilter(
-        [(img_t.data_ptr(), ishape, (ishape[1] * ishape[2], ishape[2], 1))], dtype, order, dev,
-        mode, dim, _spline.pad_value(boundary[1], img_dtype) if boundary else 0.0)
-    d.image = coeffs.data_ptr()
-  lib = _abi.load()
+  coeffs = _sample_coefficients(d, pad + tuple(image.shape), img_dtype, dev, mode,
+                                boundary[1] if boundary else None)
   if relative:
     d.rel_map = map_t.data_ptr()
     d.map_f64 = int(map_dtype == np.float64)
@@ -495,16 +486,39 @@ def ndimage_warp(image, coord_map, stride, work_size, overlap,
     if boundary is not None:
       d.has_boundary = 1
       d.mode, d.cval = boundary
-    _abi.check(lib.sfm_ndimage_warp_rel(C.byref(d)))
   else:
     d.src_map = map_t.data_ptr()
-    if boundary is not None:
-      _abi.check(lib.sfm_ndimage_warp_mode(C.byref(d), boundary[0], boundary[1]))
-    elif order in _spline.ORDERS:
-      _abi.check(lib.sfm_ndimage_warp_spline(C.byref(d)))
-    else:
-      _abi.check(lib.sfm_ndimage_warp(C.byref(d)))
+  _abi.check(_ndimage_warp_call(d, boundary, order in _spline.ORDERS))
+  del coeffs    # (read by the launch above; the stream orders its release)
   return _warped(out_t, img_dtype, device_output)
+
+
+def _sample_coefficients(d, shape, img_dtype, dev, mode, cval):
+  """Orders 2 to 5 sample B-spline coefficients: prefilters the dense image d.image
+  of zyx `shape` (ndim, dtype and order are filled in; cval None: no boundary mode)
+  and points d.image to the result, which is returned and has to live until the
+  launch is issued.  None, and `d` as it is, for orders 0 and 1."""
+  if d.order not in _spline.ORDERS:
+    return None
+  coeffs, _ = _spline.prefilter(
+      [(d.image, shape, (shape[1] * shape[2], shape[2], 1))], d.dtype, d.order, dev,
+      mode, d.ndim, 0.0 if cval is None else _spline.pad_value(cval, img_dtype))
+  d.image = coeffs.data_ptr()
+  return coeffs
+
+
+def _ndimage_warp_call(d, boundary, spline: bool) -> int:
+  """Runs the entry point of a filled descriptor: a relative map has one for all
+  cases, an absolute map one with a boundary mode, one for orders 2 to 5 and one for
+  orders 0 and 1."""
+  lib = _abi.load()
+  if isinstance(d, _abi.SfmNdWarpRelDesc):
+    return lib.sfm_ndimage_warp_rel(C.byref(d))
+  if boundary is not None:
+    return lib.sfm_ndimage_warp_mode(C.byref(d), boundary[0], boundary[1])
+  if spline:
+    return lib.sfm_ndimage_warp_spline(C.byref(d))
+  return lib.sfm_ndimage_warp(C.byref(d))
 
 
 def _absolute_map(coord_map: np.ndarray, stride, image_box, map_box, out_scale) -> np.ndarray:
@@ -606,12 +620,9 @@ def affine_transform(image, matrix, offset=0.0, order=1, mode='constant', cval=0
   d.image = img_t.data_ptr()
   d.out = out_t.data_ptr()
   d.stream = _dev.stream_ptr()
-  if order in _spline.ORDERS:
-    coeffs, _ = _spline.prefilter(
-        [(img_t.data_ptr(), shape, (shape[1] * shape[2], shape[2], 1))], dtype, order, dev,
-        mode, dim, _spline.pad_value(cval, img_dtype))
-    d.image = coeffs.data_ptr()
+  coeffs = _sample_coefficients(d, shape, img_dtype, dev, mode, cval)
   _abi.check(_abi.load().sfm_affine_warp(C.byref(d)))
+  del coeffs    # (read by the launch above; the stream orders its release)
   return _warped(out_t, img_dtype, device_output)
 
 

@@ -1,7 +1,7 @@
 """NumPy restatement of scipy.ndimage.map_coordinates and affine_transform with a
 boundary mode and a fill value, in plain float64 arithmetic and in SciPy's
 operation order.  tests/test_ndwarp_modes_ref.py pins it to SciPy bit for bit; the
-device samplers (sfm_ndsample.h) and affine_warp_kernel (sfm_warp.hip) are written
+device samplers (sfm_ndsample.h) and affine_warp_kernel (sfm_ndwarp_kernel.h) are written
 from this file.
 
 Per axis of length `len` a sample is formed in three steps:

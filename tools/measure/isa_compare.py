@@ -2,9 +2,11 @@
 """Compares the gfx950 code generation of the correlation family between two trees.
 
   isa_compare.py TREE_A TREE_B [--work DIR] [--jobs N] [--out TABLE]
+                 [--patterns GLOB ...] [--extra-flags=FLAGS]
 
 For each tree every unit of the family (csrc/sfm_xcorr*.hip, sfm_mfma*.hip,
-sfm_fft_own.hip) is compiled to device assembly with the production flags, the
+sfm_fft_own.hip; another family with --patterns, its own build flags with
+--extra-flags) is compiled to device assembly with the production flags, the
 functions are matched by demangled name with the enclosing namespaces dropped, and
 for each the instruction text (local label numbers and symbol namespaces
 normalised, comments dropped) and the .amdhsa_ lines (registers, scratch, LDS) are
@@ -25,15 +27,15 @@ PATTERNS = ('sfm_xcorr*.hip', 'sfm_mfma*.hip', 'sfm_fft_own.hip')
 NAMESPACES = re.compile(r'\(anonymous namespace\)::|\bsfm::mfma::|\bsfm::')
 
 
-def emit(tree, work, jobs):
+def emit(tree, work, jobs, patterns, extra):
   csrc = os.path.join(tree, 'sofima_amd', 'csrc')
-  units = sorted(u for p in PATTERNS for u in glob.glob(os.path.join(csrc, p)))
+  units = sorted(u for p in patterns for u in glob.glob(os.path.join(csrc, p)))
   os.makedirs(work, exist_ok=True)
 
   def one(unit):
     out = os.path.join(work, os.path.basename(unit)[:-4] + '.s')
     if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(unit):
-      subprocess.run(['hipcc'] + FLAGS + [unit, '-o', out], check=True)
+      subprocess.run(['hipcc'] + FLAGS + extra + [unit, '-o', out], check=True)
     return out
 
   with ThreadPoolExecutor(max_workers=jobs) as pool:
@@ -89,7 +91,8 @@ def functions(paths):
 
   def norm(s):
     s = re.sub(r'\b_Z\w+', lambda m: '<' + plain[m.group(0)] + '>', s)
-    s = re.sub(r'\.L(BB|tmp|func_begin|func_end|JTI)\d+', r'.L\1', s)
+    # (.Lpost_getpc<n>, the label of a long branch, is numbered through the whole unit)
+    s = re.sub(r'\.L(BB|tmp|func_begin|func_end|JTI|post_getpc)\d+', r'.L\1', s)
     return re.sub(r'\s+', ' ', s)
 
   # (a device function that is not inlined exists once per unit that calls it: one entry
@@ -113,9 +116,12 @@ def main():
   ap.add_argument('--work', default='measure_out/isa_compare')
   ap.add_argument('--jobs', type=int, default=min(os.cpu_count() or 1, 16))
   ap.add_argument('--out', default=None)
+  ap.add_argument('--patterns', nargs='+', default=list(PATTERNS))
+  ap.add_argument('--extra-flags', default='')
   args = ap.parse_args()
-  fa = functions(emit(args.tree_a, os.path.join(args.work, 'a'), args.jobs))
-  fb = functions(emit(args.tree_b, os.path.join(args.work, 'b'), args.jobs))
+  extra = args.extra_flags.split()
+  fa = functions(emit(args.tree_a, os.path.join(args.work, 'a'), args.jobs, args.patterns, extra))
+  fb = functions(emit(args.tree_b, os.path.join(args.work, 'b'), args.jobs, args.patterns, extra))
   rows = []
   bad = 0
   for name in sorted(set(fa) | set(fb)):
