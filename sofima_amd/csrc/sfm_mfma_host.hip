@@ -350,6 +350,9 @@ bool mfma_i8_eligible(const SfmXcorrDesc* d) {
     // search-window variants: un-masked, the prep kernel's LDS copy of a patch and the
     // correlation kernel's two patches + scratch within one CU's LDS
     if (d->pre_mask || d->post_mask) return false;
+    // (general mode only, launch_variant: a same-size pair 161 wide is the one shape that
+    // picks these variants and the same-size mode -- it takes another path)
+    if (same_size(d)) return false;
     if ((long long)py * px > 140 * 1024) return false;
     const Layout l = make_layout(d, kVariants[vi]);
     if ((size_t)l.a_bytes + l.b_bytes + 8 * 1024 > kLdsPerCu) return false;

@@ -1569,8 +1569,11 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
                 v = __builtin_fmaf(-mua, static_cast<float>(sb), v);
                 v = __builtin_fmaf(-mub, static_cast<float>(sa), v);
                 v = __builtin_fmaf(muab, __fmul_rn(static_cast<float>(ny[r]), fnx), v);
-                // (only the last column tile has columns past the surface)
-                const bool ok = REG == 3 ? rowok[r] && (q < NQ - 1 || kx < Sx) : rowok[r];
+                // (a variant wider than the patch has whole column tiles past the surface:
+                // their clamped shifts carry the mean correction of the last column without
+                // its product sum, which outgrows the true maximum once |mean - centre| is
+                // large -- they must reach neither the running maximum nor the hot list)
+                const bool ok = REG == 3 ? rowok[r] && kx < Sx : rowok[r];
                 if (pass == 0) {
                   __builtin_nontemporal_store(v, srow_p[r] + 16 * u);
                   tmax = fmaxf(tmax, ok ? v : 0.f);
@@ -1772,8 +1775,9 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
           const float ex = sx ? -1.f : 1.f;
           const float b_pos = ex * rca[q];  // sy = 1
           const float b_neg = ex * rcb[q];  // sy = 0
-          const float fnx = (q < NQ - 1 || kx < Sx)
-                                ? static_cast<float>(Px - abs(dx)) : NAN;
+          // (every column past the surface, not only those of the last tile: a variant
+          // wider than the patch has whole tiles of them)
+          const float fnx = kx < Sx ? static_cast<float>(Px - abs(dx)) : NAN;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float corr = fmaf(ey[r] * ex, gv[r], sx ? a_pos[r] : a_neg[r]);
@@ -1866,7 +1870,7 @@ __global__ void __launch_bounds__(NCA > 10 ? kWideThreads : kThreads,
             v = v - mub * static_cast<float>(sa);
             v = v + muab * (static_cast<float>(ny[r]) * fnx);
             surf[srow[r] + 16 * q] = v;
-            const bool ok = rowok[r] && (q < NQ - 1 || kx < Sx);
+            const bool ok = rowok[r] && kx < Sx;   // (also in the tiles before the last)
             tmax = fmaxf(tmax, ok ? v : 0.f);
             acc[q][r] = __float_as_int(ok ? v : -INFINITY);
           }
