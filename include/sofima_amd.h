@@ -1440,6 +1440,10 @@ typedef struct SfmMeshPlanInfo {
   int32_t packed;               /* ... with the narrow last tile column packed                */
   int32_t march_t;              /* z-march kernel: threads per workgroup, 0 not taken         */
   int32_t grid;                 /* workgroups of the per-node kernels                         */
+  int32_t march_ntx;            /* z-march kernel: tile columns along x and y of a volume,    */
+  int32_t march_nty;            /*   planes per workgroup, workgroups (0 where not taken)     */
+  int32_t march_run;
+  int32_t march_grid;
 } SfmMeshPlanInfo;
 
 int sfm_debug_mesh_plan(const SfmMeshDesc* desc, SfmMeshPlanInfo* info);

@@ -689,7 +689,8 @@ class SfmChunkStats(C.Structure):
 
 class SfmMeshPlanInfo(C.Structure):
   _fields_ = [('persist_tile', i32), ('persist_spec', i32), ('small', i32), ('tiled', i32),
-              ('fused', i32), ('packed', i32), ('march_t', i32), ('grid', i32)]
+              ('fused', i32), ('packed', i32), ('march_t', i32), ('grid', i32),
+              ('march_ntx', i32), ('march_nty', i32), ('march_run', i32), ('march_grid', i32)]
 
 
 # name -> (restype, argtypes); mirrors include/sofima_amd.h one to one.

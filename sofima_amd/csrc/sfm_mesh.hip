@@ -110,6 +110,13 @@ struct MeshParams {
 
 typedef sfm::MeshScalars Scalars;
 
+// max that keeps a NaN from either side (fmaxf drops it): v_max of a chunk is NaN when a
+// velocity is, like the reference's jnp.max (mesh.py:586), and `v_max < stop_v_max` then
+// stays false instead of reporting a diverged mesh as converged.
+__host__ __device__ __forceinline__ float nan_max(float a, float b) {
+  return (a >= b || a != a) ? a : b;
+}
+
 // Correctly rounded square root and division without the sub-normal scaling of
 // the compiler's IEEE sequences (15 -> 9 and 11 -> 8 instructions; the spring
 // evaluations are VALU bound).  Results are bit-identical to sqrtf() / operator/
@@ -1844,7 +1851,7 @@ finish_kernel(float* __restrict__ x, float* __restrict__ v, MeshParams p,
     const int yrow = static_cast<int>((n / p.X) % p.Y);
     if (yrow >= p.own_y0 && yrow < p.own_y1) {
       ek = ek + v2;
-      vmax2 = fmaxf(vmax2, v2);
+      vmax2 = nan_max(vmax2, v2);
     }
   }
   lds[threadIdx.x] = ek;
@@ -1854,7 +1861,7 @@ finish_kernel(float* __restrict__ x, float* __restrict__ v, MeshParams p,
     if (threadIdx.x < st) {
       lds[threadIdx.x] = lds[threadIdx.x] + lds[threadIdx.x + st];
       lds[kBlock + threadIdx.x] =
-          fmaxf(lds[kBlock + threadIdx.x], lds[kBlock + threadIdx.x + st]);
+          nan_max(lds[kBlock + threadIdx.x], lds[kBlock + threadIdx.x + st]);
     }
     __syncthreads();
   }
@@ -1871,7 +1878,7 @@ stats_kernel(const float* __restrict__ stat_partials, int rows,
   float ek = 0.f, vm = 0.f;
   for (int r = threadIdx.x; r < rows; r += kBlock) {
     ek = ek + stat_partials[r * 2];
-    vm = fmaxf(vm, stat_partials[r * 2 + 1]);
+    vm = nan_max(vm, stat_partials[r * 2 + 1]);
   }
   lds[threadIdx.x] = ek;
   lds[kBlock + threadIdx.x] = vm;
@@ -1880,7 +1887,7 @@ stats_kernel(const float* __restrict__ stat_partials, int rows,
     if (threadIdx.x < st) {
       lds[threadIdx.x] = lds[threadIdx.x] + lds[threadIdx.x + st];
       lds[kBlock + threadIdx.x] =
-          fmaxf(lds[kBlock + threadIdx.x], lds[kBlock + threadIdx.x + st]);
+          nan_max(lds[kBlock + threadIdx.x], lds[kBlock + threadIdx.x + st]);
     }
     __syncthreads();
   }
@@ -2158,7 +2165,7 @@ __device__ __forceinline__ void persist_write_back(const TileFrame<T>& fr, const
 #pragma unroll
   for (int dd = 32; dd > 0; dd >>= 1) {
     ek = ek + __shfl_xor(ek, dd, 64);
-    vm2 = fmaxf(vm2, __shfl_xor(vm2, dd, 64));
+    vm2 = nan_max(vm2, __shfl_xor(vm2, dd, 64));
   }
   __syncthreads();
   if (lane == 0 && wave < Tile<T>::kWavesT) {
@@ -2170,7 +2177,7 @@ __device__ __forceinline__ void persist_write_back(const TileFrame<T>& fr, const
     float e = 0.f, m = 0.f;
     for (int w2 = 0; w2 < Tile<T>::kWavesT; ++w2) {
       e = e + red[w2 * 2];
-      m = fmaxf(m, red[w2 * 2 + 1]);
+      m = nan_max(m, red[w2 * 2 + 1]);
     }
     q.stat_partials[wg * 2] = e;
     q.stat_partials[wg * 2 + 1] = m;
@@ -3707,6 +3714,10 @@ int sfm_debug_mesh_plan(const SfmMeshDesc* d, SfmMeshPlanInfo* info) {
   info->packed = c.tiled && c.pack;
   info->march_t = c.march.T;
   info->grid = c.grid;
+  info->march_ntx = c.march.T ? c.march.g.ntx : 0;
+  info->march_nty = c.march.T ? c.march.g.nty : 0;
+  info->march_run = c.march.T ? c.march.g.run : 0;
+  info->march_grid = c.march.T ? c.march.grid : 0;
   return SFM_OK;
 }
 
@@ -4409,7 +4420,7 @@ struct BandedRun {
     float ek = 0.f, vm = 0.f;
     for (int g = 0; g < total; ++g) {   // band order, float32 like the device sums
       ek = ek + hs[2 * g];
-      vm = std::max(vm, hs[2 * g + 1]);
+      vm = nan_max(vm, hs[2 * g + 1]);
     }
     stats->e_kin = ek;
     stats->v_max = vm;

@@ -47,6 +47,8 @@ and asserts that the values below still cover them; never taken from a kernel):
   K_S   the same for x, v, a after 1 .. 3 steps over step_cases(), in units of
         2^-24 * scale: scale(x), scale(v) = largest |float64 value| of the array,
         scale(a) = largest S(n) + k0 |x - prev| (it does not vanish at equilibrium)
+  K_E   largest error of a float32 sum, one term after the other, of the float32 form's
+        |v_n|^2 terms against their float64 sum, in units of 2^-24 e_kin (stat_bounds)
 
 The device is allowed 4 x: the project's usual margin (ATOL32 = 4 x MEASURED_DEV32),
 for one-ulp differences between correctly rounded sequences and other summation
@@ -63,9 +65,11 @@ import numpy as np
 f32 = np.float32
 EPS = 2.0 ** -24
 
-# Measured by tests/test_mesh_ref64.py on the CPU (2.357; 3.140, 53.74, 1.053), rounded up.
+# Measured by tests/test_mesh_ref64.py on the CPU (2.357; 3.613, 53.74, 1.053; 95.47),
+# rounded up.  (K_S['x'] was 3.2, measured 3.140, before the volumetric and chunk cases.)
 K_F = 2.4
-K_S = {'x': 3.2, 'v': 54.0, 'a': 1.1}
+K_S = {'x': 3.7, 'v': 54.0, 'a': 1.1}
+K_E = 96.0
 DEV_FACTOR = 4.0
 
 LINKS_3D = (
@@ -228,12 +232,16 @@ class Cfg:
   remove_drift: bool = False
 
 
-def fire_next(dt, alpha, n_pos, cap, downhill, cfg):
-  """The FIRE scalar update (mesh.py:459-490), in float32 like the kernel's fire_next."""
+def fire_next(dt, alpha, n_pos, cap, downhill, cfg, dt_lim=None):
+  """The FIRE scalar update (mesh.py:459-490), in float32 like the kernel's fire_next.
+  dt is limited by dt_max x config.dt whatever dt the chunk started from (`dt_lim` is
+  for the wrong results of tests/test_mesh_ref64.py only)."""
   n_pos = n_pos + 1 if downhill else 0
+  if dt_lim is None:
+    dt_lim = f32(float(cfg.dt_max) * float(cfg.dt))
   if downhill:
     if n_pos > cfg.n_min:
-      dt = min(f32(dt * f32(cfg.f_inc)), f32(float(cfg.dt_max) * float(cfg.dt)))
+      dt = min(f32(dt * f32(cfg.f_inc)), dt_lim)
       alpha = f32(alpha * f32(cfg.f_alpha))
     if n_pos > 0 and n_pos % max(int(cfg.cap_upscale_every), 1) == 0:
       cap = f32(f32(cfg.cap_scale) * cap)
@@ -244,17 +252,42 @@ def fire_next(dt, alpha, n_pos, cap, downhill, cfg):
   return f32(dt), f32(alpha), n_pos, f32(cap)
 
 
-def step(x, v, prev, cfg, force_cap, n, dtype=np.float64, links=None, scales=None):
-  """`n` <= 3 steps of mesh.velocity_verlet.  Returns (x, v, a, dt, alpha, n_pos,
-  cap); the four scalars are float32 / int with FIRE and None without.  `scales`, a
-  dict, receives the error scales of x, v and a (see the module docstring).
+def _widen(t, dtype):
+  """The float32 array a kernel gets, in `dtype`; a float64 array is the float64
+  statement's own state between two chunks and stays as it is."""
+  t = np.asarray(t)
+  if t.dtype == np.float64 and dtype == np.float64:
+    return t
+  return np.asarray(t, f32).astype(dtype)
+
+
+def step(x, v, prev, cfg, force_cap, n, dtype=np.float64, links=None, scales=None,
+         dt0=None, alpha0=None, taps=None, _wrong=None):
+  """`n` <= 3 steps of mesh.velocity_verlet: one chunk.  Returns (x, v, a, dt, alpha,
+  n_pos, cap); the four scalars are float32 / int with FIRE and None without.  `scales`,
+  a dict, receives the error scales of x, v and a (see the module docstring).
+
+  `dt0` / `alpha0` are the chunk's starting fire_dt / fire_alpha (default cfg.dt,
+  cfg.alpha); n_pos starts at 0 in every chunk (mesh.py:513), the first force is taken
+  with `force_cap`, and dt stays limited by f32(dt_max * cfg.dt), not by dt0.
+
+  States may be 5-D [3, B, z, y, x]: the force treats every axis in front of (z, y, x)
+  as a batch, and the drift means are over axes (1, 2, 3) as the reference hard-codes
+  them (mesh.py:496-497) -- global for a 4-D state, one mean per x column over
+  (B, z, y) for a 5-D one.
 
   With FIRE every step asserts |power| > 1e-3 |a| |v| (or an exactly zero state):
   the branch taken does not depend on round-off.
+
+  `taps`, a dict, receives the last step's velocity before the gate (`v_gate`) and
+  before the drift removal (`v_drift`).  `_wrong` (a dict) makes the deliberately wrong
+  results that tests/test_mesh_ref64.py feeds to the checks: `pending_lost`,
+  `drift_axes`, `n_pos0`, `dt_carried`, `a0_cap`.  Never used for an expectation.
   """
   assert 0 <= n <= 3
-  x = np.asarray(x, f32).astype(dtype)
-  v = np.asarray(v, f32).astype(dtype)
+  wrong = _wrong or {}
+  x = _widen(x, dtype)
+  v = _widen(v, dtype)
   pv = None if prev is None else np.asarray(prev, f32).astype(dtype)
   poo = cfg.prefer_orig_order
   s_a = [0.0]
@@ -274,11 +307,12 @@ def step(x, v, prev, cfg, force_cap, n, dtype=np.float64, links=None, scales=Non
   half, one = dtype(0.5), dtype(1.0)
   g = dtype(f32(cfg.gamma))
   cap = f32(force_cap)
-  a = total(x, cap)
-  dt = f32(cfg.dt)
-  alpha = f32(cfg.alpha)
-  n_pos = 0
-  for _ in range(n):
+  a = total(x, f32(wrong.get('a0_cap', cap)))
+  dt = f32(cfg.dt if dt0 is None else dt0)
+  alpha = f32(cfg.alpha if alpha0 is None else alpha0)
+  dt_lim = f32(float(cfg.dt_max) * float(dt)) if wrong.get('dt_carried') else None
+  n_pos = int(wrong.get('n_pos0', 0))
+  for it in range(n):
     dtw = dtype(dt)
     x = x + (dtw * v + (half * (dtw * dtw)) * a)
     a_new = total(x, cap)
@@ -294,19 +328,77 @@ def step(x, v, prev, cfg, force_cap, n, dtype=np.float64, links=None, scales=Non
       size = float(np.linalg.norm(a.astype(np.float64)) * np.linalg.norm(v.astype(np.float64)))
       v = v + dtype(alpha) * (a / a_n * v_n - v)
     assert abs(power) > 1e-3 * size or (power == 0 and size == 0), (power, size)
+    if taps is not None and it == n - 1:
+      taps['v_gate'] = v
+    if wrong.get('pending_lost') and it == n - 1:
+      continue
     downhill = power >= 0
-    dt, alpha, n_pos, cap = fire_next(dt, alpha, n_pos, cap, downhill, cfg)
+    dt, alpha, n_pos, cap = fire_next(dt, alpha, n_pos, cap, downhill, cfg, dt_lim)
     v = v * dtype(1.0 if downhill else 0.0)
+    if taps is not None and it == n - 1:
+      taps['v_drift'] = v
     if cfg.remove_drift:
       # the reference hard-codes axes (1, 2, 3) (mesh.py:496-497)
-      x = x - x.mean(axis=(1, 2, 3), keepdims=True, dtype=dtype)
-      v = v - v.mean(axis=(1, 2, 3), keepdims=True, dtype=dtype)
+      axes = wrong.get('drift_axes', (1, 2, 3))
+      x = x - x.mean(axis=axes, keepdims=True, dtype=dtype)
+      v = v - v.mean(axis=axes, keepdims=True, dtype=dtype)
   if scales is not None:
     top = lambda t: float(np.abs(np.nan_to_num(t, posinf=0.0, neginf=0.0)).max())
     scales.update(x=top(x), v=top(v), a=s_a[0])
   if not cfg.fire:
     return x, v, a, None, None, None, None
   return x, v, a, f32(dt), f32(alpha), int(n_pos), f32(cap)
+
+
+def chunk_stats(v):
+  """(e_kin, v_max) as relax_mesh forms them from a chunk's velocities (mesh.py:584-586):
+  sum of |v_n|^2 and largest |v_n| over the nodes, in float64."""
+  v2 = np.sum(np.asarray(v, np.float64) ** 2, axis=0)
+  return float(v2.sum()), float(np.sqrt(v2.max()))
+
+
+def assert_v_max_margin(v_max, stop_v_max):
+  """A condition on a chunk case's inputs: the float64 v_max is exactly 0 or at least
+  1 % away from stop_v_max, so the stop rule does not depend on round-off."""
+  assert v_max == 0 or abs(v_max - stop_v_max) >= 0.01 * stop_v_max, (v_max, stop_v_max)
+
+
+def relax_chunks(case, n_chunks, dtype=np.float64, _wrong=None):
+  """The chunk loop of relax_mesh (mesh.py:570-606) around `step`, from v = 0: x and v
+  pass from chunk to chunk, dt / alpha / cap are carried with FIRE, n_pos restarts and
+  the first force of every chunk is taken again with the carried cap.  Stops on
+  max_iters, or on v_max < stop_v_max once the cap has reached final_cap (compared in
+  float32 like mesh._relax_loop); below final_cap it raises the cap to
+  min(cap * cap_scale, final_cap) instead.
+
+  Returns ([(x, v, a, (dt, alpha, n_pos, cap), e_kin, v_max, scales, (dt0, alpha0,
+  cap0))] per chunk, the e_kin list, t).  At most `n_chunks` chunks and three steps
+  in all: the n <= 3 contract of `step`, and the meaning of K_S, hold.
+  """
+  cfg = case.cfg
+  x, v = case.x, np.zeros_like(case.x)
+  t, dt, alpha, cap = 0, f32(cfg.dt), f32(cfg.alpha), f32(cfg.start_cap)
+  chunks, e_kin = [], []
+  while t < cfg.max_iters:
+    assert len(chunks) < n_chunks and t + cfg.num_iters <= 3, (case.name, t)
+    scales = {}
+    start = (dt, alpha, cap)
+    out = step(x, v, case.prev, cfg, cap, cfg.num_iters, dtype, case.links, scales,
+               dt0=dt, alpha0=alpha, _wrong=_wrong)
+    t += cfg.num_iters
+    x, v = out[:2]
+    e, v_max = chunk_stats(v)
+    if dtype == np.float64:
+      assert_v_max_margin(v_max, cfg.stop_v_max)
+    e_kin.append(e)
+    if cfg.fire:
+      dt, alpha, cap = out[3], out[4], out[6]
+    chunks.append((x, v, out[2], out[3:], e, v_max, scales, start))
+    if v_max < cfg.stop_v_max:
+      if f32(cap) >= f32(cfg.final_cap):
+        break
+      cap = f32(min(float(cap) * float(cfg.cap_scale), float(cfg.final_cap)))
+  return chunks, e_kin, t
 
 
 # ---------------------------------------------------------------------------
@@ -487,6 +579,28 @@ STEP_CONFIGS = ('verlet', 'fire_down', 'fire_up', 'fire_drift')
 PREV_KINDS = ('prev', 'prev_nan', 'none')
 
 
+# Volumetric first steps: each the smallest shape that reaches the edge named.
+VOL_SHAPES = (
+    (3, 3, 4, 5),          # an interior node with all 26 springs; still mesh_small_kernel
+    (3, 5, 7, 9),          # 315 nodes: past the small limit, two workgroups per node kernel
+    (3, 1, 3, 4, 5), (3, 2, 3, 4, 5),        # 5-D: drift per x column, G = 51 row groups
+    (3, 1, 2, 3, 256), (3, 1, 2, 3, 257),    # drift_cols_kernel at G = 1, two passes over x
+    (3, 3, 7, 100), (3, 2, 3, 7, 100),       # z-march at T = 256: several tile columns in x
+    (3, 3, 20, 100),       # ... and 5 x 2 tiles (plan_march3d takes 4 x 1 for Y = 7)
+    (3, 1, 6, 40), (3, 4, 1, 40), (3, 4, 6, 1))          # z-march with an axis of 1
+VOL_LINK_SHAPES = ((3, 3, 4, 5), (3, 5, 7, 9), (3, 2, 3, 4, 5), (3, 1, 2, 3, 257))
+# Above 50 000 nodes: fire_down and fire_drift, prev_nan, n = 2, one prefer_orig_order each.
+LARGE_SHAPES = (
+    (3, 2, 9, 30, 100),    # 540 rows at G = 2: 17 chunks, a second closing batch of 16
+    (3, 2, 16, 65, 100),   # 2080 rows: the 64-chunk cap, rows_per no multiple of G * 16
+    GRID_STRIDE[1],        # 270 400 nodes: grid-stride step kernels, 1024 partial rows
+    GRID_STRIDE[0])        # the same in-plane (multi-launch and tiled)
+CHUNK_SHAPES = ((2, 1, 4, 40), (2, 2, 17, 63), (3, 3, 4, 5), (3, 2, 3, 4, 5))
+CHUNK_KINDS = ('second_chunk', 'cap_raise3', 'cap_raise2')
+SECOND_DT0 = f32(0.3 * 1.1 ** 2)
+SECOND_ALPHA0 = f32(0.1 * 0.99 ** 2)
+
+
 @dataclasses.dataclass(frozen=True, eq=False)
 class StepCase:
   name: str
@@ -496,6 +610,8 @@ class StepCase:
   cfg: Cfg
   force_cap: float
   links: tuple | None = None
+  dt0: float | None = None      # the chunk's starting fire_dt / fire_alpha (None: cfg's)
+  alpha0: float | None = None
 
   @property
   def n(self):
@@ -511,6 +627,18 @@ def _step_cfg(kind, stride, n, poo):
     # dt, alpha and the cap move on every step: cap 1 -> 1.5 -> 2 (= final_cap)
     base.update(n_min=0, cap_upscale_every=1, start_cap=1.0, final_cap=2.0, cap_scale=1.5,
                 remove_drift=kind == 'fire_drift')
+  if kind == 'second_chunk':
+    # dt_max * cfg.dt = 0.39 binds on the first growth (0.363 * 1.1 = 0.3993)
+    base.update(dt_max=1.3)
+  if kind in CHUNK_KINDS:
+    # |x - prev| reaches 13.5: with k0 = 0.2 the pull is clipped at every cap from 1 to 2
+    # (the first force of a chunk depends on the cap it is taken with)
+    base.update(k0=0.2)
+  if kind.startswith('cap_raise'):
+    # one step per chunk; only the chunk loop raises the cap: 1 -> 1.5 -> 2.  With
+    # max_iters = 3 the third chunk runs at final_cap and the loop stops on the cap,
+    # with max_iters = 2 it stops on max_iters with the cap raised once more, unused.
+    base.update(num_iters=1, max_iters=int(kind[-1]), stop_v_max=1e9, cap_upscale_every=100)
   return Cfg(**base)
 
 
@@ -530,13 +658,20 @@ def step_case(shape, kind, prev_kind, n, poo, links=None):
       prev[..., 0, :] = np.nan
   cfg = _step_cfg(kind, stride, n, poo)
   v = np.zeros(shape, f32)
+  cap, dt0, alpha0 = cfg.start_cap, None, None
   if kind == 'fire_up':
     # against the first force: the first update halves dt, zeroes v, resets alpha
     a0 = step(x, v, prev, cfg, cfg.start_cap, 0, np.float64, links)[2]
     v = (-0.5 * a0).astype(f32)
+  if kind == 'second_chunk':
+    # what a first chunk of two downhill steps hands over: dt and alpha grown twice,
+    # the cap at 1.5, a downhill velocity
+    cap, dt0, alpha0 = 1.5, SECOND_DT0, SECOND_ALPHA0
+    a0 = step(x, v, prev, cfg, cap, 0, np.float64, links)[2]
+    v = (0.5 * a0).astype(f32)
   for arr in (x, v) + (() if prev is None else (prev,)):
     arr.setflags(write=False)
-  return StepCase(name, x, v, prev, cfg, cfg.start_cap, links)
+  return StepCase(name, x, v, prev, cfg, cap, links, dt0, alpha0)
 
 
 @functools.lru_cache(maxsize=None)
@@ -544,10 +679,22 @@ def step_refs(case):
   """(float64 result tuple, scales dict) of a StepCase; computed once."""
   scales = {}
   want = step(case.x, case.v, case.prev, case.cfg, case.force_cap, case.n, np.float64,
-              case.links, scales)
+              case.links, scales, dt0=case.dt0, alpha0=case.alpha0)
   for arr in want[:3]:
     arr.setflags(write=False)
+  e_kin, v_max = chunk_stats(want[1])
+  assert_v_max_margin(v_max, case.cfg.stop_v_max)
   return want, scales
+
+
+@functools.lru_cache(maxsize=None)
+def relax_refs(case):
+  """relax_chunks of a cap_raise case in float64; computed once."""
+  chunks, e_kin, t = relax_chunks(case, 3)
+  for ch in chunks:
+    for arr in ch[:3]:
+      arr.setflags(write=False)
+  return chunks, e_kin, t
 
 
 def step_cases_2d(shape):
@@ -565,13 +712,61 @@ def step_cases_3d(shape, links=None):
           for poo in (False, True)]
 
 
+def step_cases_vol(shape, links=None):
+  """The full in-plane matrix on a volumetric shape."""
+  return [step_case(shape, kind, pk, n, poo, links)
+          for kind in STEP_CONFIGS for pk in PREV_KINDS for n in (1, 2, 3)
+          for poo in (False, True)]
+
+
+def step_cases_large(shape):
+  poo = bool(LARGE_SHAPES.index(shape) % 2)
+  return [step_case(shape, kind, 'prev_nan', 2, poo) for kind in ('fire_down', 'fire_drift')]
+
+
+def second_chunk_cases(shape, links=None):
+  return [step_case(shape, 'second_chunk', pk, n, poo, links)
+          for pk in ('prev', 'prev_nan') for n in (1, 2) for poo in (False, True)]
+
+
+def cap_raise_cases(shape, links=None):
+  return [step_case(shape, kind, 'prev', 1, poo, links)
+          for kind in ('cap_raise3', 'cap_raise2') for poo in (False, True)]
+
+
+def uphill_end_cases(shape, links=None):
+  """Chunks whose last step is uphill: v is gated to exactly 0."""
+  return [step_case(shape, 'fire_up', pk, 1, poo, links)
+          for pk in PREV_KINDS for poo in (False, True)]
+
+
 def step_cases():
+  """Every single-chunk case (the cap_raise cases run through relax_chunks)."""
   out = []
   for shape in STEP_SHAPES_2D:
     out += step_cases_2d(shape)
   for shape in DEGENERATE_3D:
     out += step_cases_3d(shape)
     out += step_cases_3d(shape, STEP_LINKS_3D)
+  for shape in VOL_SHAPES:
+    out += step_cases_vol(shape)
+  for shape in VOL_LINK_SHAPES:
+    out += step_cases_vol(shape, STEP_LINKS_3D)
+  for shape in LARGE_SHAPES:
+    out += step_cases_large(shape)
+  for shape in CHUNK_SHAPES:
+    out += second_chunk_cases(shape)
+    if shape[0] == 3:
+      out += second_chunk_cases(shape, STEP_LINKS_3D)
+  return out
+
+
+def relax_cases():
+  out = []
+  for shape in CHUNK_SHAPES:
+    out += cap_raise_cases(shape)
+    if shape[0] == 3:
+      out += cap_raise_cases(shape, STEP_LINKS_3D)
   return out
 
 
@@ -609,4 +804,87 @@ def check_force(got, name, poo, factor=DEV_FACTOR, bitwise=True):
   assert u <= factor * K_F, (name, poo, u)
   if bitwise:
     assert np.array_equal(got, form), (name, poo, units(got, form, S[None]))
+  return u
+
+
+def check_state(got, want, scales, what, factor=DEV_FACTOR):
+  """x, v, a (the first three of `got`) within factor x K_S of the float64 ones.
+  Returns the units measured."""
+  out = {}
+  for i, key in enumerate('xva'):
+    g = np.asarray(got[i])
+    assert g.shape == want[i].shape and not np.isnan(g).any(), (what, key)
+    out[key] = units(g, want[i], scales[key])
+    assert out[key] <= factor * K_S[key], (what, key, out[key])
+  return out
+
+
+def check_step(got, case, what='', factor=DEV_FACTOR):
+  """The assertions on one chunk's result (x, v, a[, dt, alpha, n_pos, cap]) against the
+  float64 statement: the arrays within factor x K_S, the FIRE scalars equal."""
+  want, scales = step_refs(case)
+  u = check_state(got, want, scales, (what, case.name), factor)
+  if case.cfg.fire:
+    # dt, alpha, n_pos, cap: float32 like fire_next, compared with ==
+    assert tuple(got[3:7]) == tuple(want[3:]), (what, case.name, got[3:7], want[3:])
+  else:
+    assert len(got) == 3 or got[3] is None, (what, case.name)
+  return u
+
+
+def stat_bounds(v64, scale_v):
+  """(e_kin, v_max, allowed |error| of e_kin, of v_max) for a chunk whose float64
+  velocities are `v64`.  delta = DEV_FACTOR K_S['v'] 2^-24 scale(v) is what a device
+  velocity component may be off by.  The node norm is 1-Lipschitz in the components
+  (sqrt(C) delta), and its square, sum and root round twice at most (2 x 2^-24 v_max);
+  |v + d|^2 - |v|^2 <= 2 |v| d + d^2 per component, and the float32 sum of the terms
+  is allowed DEV_FACTOR x K_E, K_E being the error of the worst (sequential) order."""
+  v64 = np.asarray(v64, np.float64)
+  e_kin, v_max = chunk_stats(v64)
+  delta = DEV_FACTOR * K_S['v'] * EPS * scale_v
+  tol_v = np.sqrt(v64.shape[0]) * delta + 2 * EPS * v_max
+  tol_e = float(np.sum(2 * np.abs(v64) * delta + delta * delta)) + DEV_FACTOR * K_E * EPS * e_kin
+  return e_kin, v_max, tol_e, tol_v
+
+
+def check_stats(e_kin, v_max, v64, scale_v, what=''):
+  """The assertions on a chunk's statistics (what relax_mesh stops on).  Where the
+  float64 velocities are all 0 (a chunk that ends uphill), both are exactly 0."""
+  want_e, want_v, tol_e, tol_v = stat_bounds(v64, scale_v)
+  e_kin, v_max = float(e_kin), float(v_max)
+  assert np.isfinite(e_kin) and np.isfinite(v_max), (what, e_kin, v_max)
+  if want_v == 0:
+    assert e_kin == 0.0 and v_max == 0.0, (what, e_kin, v_max)
+    return 0.0, 0.0
+  assert abs(e_kin - want_e) <= tol_e, (what, 'e_kin', e_kin, want_e, tol_e)
+  assert abs(v_max - want_v) <= tol_v, (what, 'v_max', v_max, want_v, tol_v)
+  return abs(e_kin - want_e) / tol_e, abs(v_max - want_v) / tol_v
+
+
+def check_case_stats(e_kin, v_max, case, what=''):
+  want, scales = step_refs(case)
+  return check_stats(e_kin, v_max, want[1], scales['v'], (what, case.name))
+
+
+def check_relax(x, e_kin, t, case, what='', starts=None, ends=None):
+  """relax_mesh on a cap_raise case against relax_chunks: t and the number of chunks
+  equal, every e_kin[i] within its bound, the final positions within DEV_FACTOR x
+  K_S['x'].  `starts` / `ends`: the (dt, alpha, cap) every chunk was started with and
+  the (dt, alpha, n_pos, cap) it returned, compared with ==."""
+  chunks, want_e, want_t = relax_refs(case)
+  what = (what, case.name)
+  assert t == want_t and len(e_kin) == len(want_e), (what, t, want_t, len(e_kin))
+  for i, ch in enumerate(chunks):
+    want_v, tol_e = ch[5], stat_bounds(ch[1], ch[6]['v'])[2]
+    assert np.isfinite(e_kin[i]) and abs(e_kin[i] - want_e[i]) <= tol_e, \
+        (what, i, e_kin[i], want_e[i], tol_e)
+    if starts is not None:
+      assert tuple(f32(s) for s in starts[i]) == tuple(ch[7]), (what, i, starts[i], ch[7])
+    if ends is not None:
+      assert tuple(ends[i]) == tuple(ch[3]), (what, i, ends[i], ch[3])
+  last = chunks[-1]
+  x = np.asarray(x)
+  assert not np.isnan(x).any(), what
+  u = units(x, last[0], last[6]['x'])
+  assert u <= DEV_FACTOR * K_S['x'], (what, 'x', u)
   return u

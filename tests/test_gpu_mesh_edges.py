@@ -172,16 +172,9 @@ def _multi(case):
 
 
 def _check_vs_float64(got, case, what):
-  want, scales = ref.step_refs(case)
-  for i, key in enumerate('xva'):
-    assert not np.isnan(got[i]).any(), (what, case.name, key)
-    u = ref.units(got[i], want[i], scales[key])
-    assert u <= ref.DEV_FACTOR * ref.K_S[key], (what, case.name, key, u)
-  if case.cfg.fire:
-    # dt, alpha, n_pos, cap: float32 like fire_next, compared with ==
-    assert tuple(got[3:]) == tuple(want[3:]), (what, case.name, got[3:], want[3:])
-  else:
-    assert len(got) == 3
+  # x, v, a within DEV_FACTOR x K_S; dt, alpha, n_pos, cap compared with ==
+  ref.check_step(got, case, what)
+  assert len(got) == (7 if case.cfg.fire else 3)
 
 
 _SHAPE_PATHS = [(s, p) for s in ref.STEP_SHAPES_2D for p in PATHS if _can_take(p, s)]
